@@ -10,21 +10,28 @@ gathered) + KP (exact tally, posterior and call of the survivors) + KO (position
 position) mapping) + D2H of the called sites + the host collect (libngsep_amd.so ngsep_submit_staged /
 ngsep_collect_staged, two passes in flight).
 
-Beside the resident rate the line carries:
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets the layout up, warms up, times the N steps and prints
+the line with the resident rate and the roofline figures of those steps.  --dump-outputs DIR then also writes what
+the last timed step handed back (dump_outputs below).  The further legs (end_to_end, cpu_baseline, the cache-flushed
+passes, the N-GPU sharded leg) are runs of their own and come with --full; --no-cold, --no-e2e and --no-cpu-baseline
+leave single ones out of a --full run.
+
+The line carries:
   * roofline   -- SURVEY.md 8(d)'s algorithmic bytes per launch (1 B per read base + 1 B of reference per
                   genotyped position + 16 B per read) / KL's average launch time from HIP events bound to
                   its dispatch; `bytes_moved_per_launch` = what KL actually reads (units incl. padding,
                   8-B headers, group and block tables, reference codes); `traffic` = HBM bytes per launch
-                  from the committed rocprofv3 PMC passes (profiles/pmc_traffic*.json);
-  * end_to_end -- BAM on disk -> VCF on disk through ngsep_call_bam (path B: BGZF decode, admission,
+                  from the committed rocprofv3 PMC passes (profiles/pmc_traffic*.json); `cold` (--full) = passes
+                  after a 1 GiB device fill;
+  * end_to_end (--full) -- BAM on disk -> VCF on disk through ngsep_call_bam (path B: BGZF decode, admission,
                   projection, layout, H2D, kernels, VCF), wall time and positions/s;
-  * cpu_baseline -- the oracle (C restatement of the reference, SAM -> VCF) on a bounded sample of the
+  * cpu_baseline (--full) -- the oracle (C restatement of the reference, SAM -> VCF) on a bounded sample of the
                   same workload, single-thread and one process per core.
 
 --gpus N > 1: one process per GPU (spawned here under torch.distributed.run when WORLD_SIZE is unset), the same
 workload per GPU as at N = 1 (the default chr20: each rank its own chr20-sized genome, seed 3 + rank -- independent
 genomic windows, no data-path collective, "weak"), so the 1/2/4/8 values divide: value = every rank's positions x
-steps / the slowest rank's time.  At N > 1 the line also carries the CPU baseline (rank 0, before any GPU call), the
+steps / the slowest rank's time.  At N > 1 with --full the line also carries the CPU baseline (rank 0, before any GPU call), the
 end-to-end leg on every rank (its own BAM -> VCF, slowest rank, positions summed) and a strong-scaling leg
 (sharded_end_to_end: ONE chr20 BAM cut into exact windows over the ranks).  --config wgs: BASELINE.json configs[3],
 the GRCh38 sequences (30x) split over the ranks by sharding.assign_contigs (the genome is fixed: "strong"; at N = 1
@@ -208,6 +215,79 @@ def load_traffic(workload_key: str):
     return None
 
 
+DUMP_CAP_BYTES = 64_000_000 - 4096      # --dump-outputs: array data in all (the .npy headers fit beside it)
+
+
+def _records(ctypes_array, n: int):
+    """the first n records of a ctypes structure array as a numpy structured array (a view, no copy)"""
+    import numpy as np
+    return np.frombuffer(ctypes_array, dtype=np.dtype(ctypes_array._type_), count=n)
+
+
+def _write_fields(out_dir: str, prefix: str, rec):
+    """one float64 array per field of a structured array (every field is an integer of at most 32 bits or a double, so
+    float64 holds it exactly); returns the bytes written as array data"""
+    import numpy as np
+    total = 0
+    for name in rec.dtype.names:
+        if name == "pad":
+            continue
+        a = np.ascontiguousarray(rec[name], dtype=np.float64)
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), a)
+        total += a.nbytes
+    return total
+
+
+def dump_outputs(sessions, multi: bool, out_dir: str):
+    """--dump-outputs: the result of the last timed step as a caller of the timed path fetches it after
+    ngsep_collect_staged / ngsep_run_staged -- ngsep_fetch_sites' records (multisample: ngsep_fetch_population_sites'
+    sites and per-sample calls), the device runs' records one after the other.  One float64 array per record field:
+    <field>.npy with a row per site (multisample: site_<field>.npy, and call_<field>.npy with a row per site and a
+    column per sample).  At most 64 MB of array data: past that, a fixed seeded sample of the sites, in position
+    order, their indexes in rows.npy."""
+    import ctypes
+    import numpy as np
+    from ngsepcore_amd._lib import NgsepPopSiteOut, NgsepSampleCall, NgsepSiteOut
+    os.makedirs(out_dir, exist_ok=True)
+    site_parts, call_parts = [], []
+    for s in sessions:
+        n = ctypes.c_int64()
+        if multi:
+            S = len(s.samples)
+            s._check(s._lib.ngsep_fetch_population_sites(s._ctx, None, None, 0, ctypes.byref(n)))
+            sites = (NgsepPopSiteOut * max(n.value, 1))()
+            calls = (NgsepSampleCall * max(n.value * S, 1))()
+            s._check(s._lib.ngsep_fetch_population_sites(s._ctx, sites, calls, n.value, ctypes.byref(n)))
+            call_parts.append(_records(calls, n.value * S).reshape(n.value, S))
+        else:
+            s._check(s._lib.ngsep_fetch_sites(s._ctx, None, 0, ctypes.byref(n)))
+            sites = (NgsepSiteOut * max(n.value, 1))()
+            s._check(s._lib.ngsep_fetch_sites(s._ctx, sites, n.value, ctypes.byref(n)))
+        site_parts.append(_records(sites, n.value))
+    sites = np.concatenate(site_parts)
+    calls = np.concatenate(call_parts) if multi else None
+
+    def numbers(dt):        # float64 values one record of this structure becomes
+        one = np.zeros(1, dtype=dt)
+        return sum(one[name].size for name in dt.names if name != "pad")
+    row_bytes = 8 * (numbers(sites.dtype) + (calls.shape[1] * numbers(calls.dtype) if multi else 0) + 1)
+    n = len(sites)
+    keep = DUMP_CAP_BYTES // row_bytes
+    total = 0
+    if n > keep:
+        rows = np.sort(np.random.default_rng(20).choice(n, size=keep, replace=False))
+        sites = sites[rows]
+        calls = calls[rows] if multi else None
+        rows = rows.astype(np.float64)
+        np.save(os.path.join(out_dir, "rows.npy"), rows)
+        total += rows.nbytes
+    total += _write_fields(out_dir, "site_" if multi else "", sites)
+    if multi:
+        total += _write_fields(out_dir, "call_", calls)
+    assert total <= DUMP_CAP_BYTES
+    log(f"dumped {len(sites)} of {n} sites ({total / 1e6:.1f} MB) into {out_dir}")
+
+
 def end_to_end(fa: str, bam: str, device: int):
     """BAM on disk -> VCF on disk: SingleSampleVariantsDetector.findSNVS through ngsep_call_bam in a fresh
     context (decode, admission, projection, layout, H2D, kernels, VCF writing), wall time."""
@@ -331,6 +411,18 @@ def bench_coverage(args):
         sess.run_staged()
         ks.append(sess.stats().scan_ms)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        # what ngsep_fetch_coverage hands back after the last step: the two histograms (the context adds every pass
+        # since it was opened into them, the warm-up's too) and their high-coverage counts
+        import ctypes
+        import numpy as np
+        n = p.max_coverage
+        a, u = (ctypes.c_int64 * n)(), (ctypes.c_int64 * n)()
+        hi, hu = ctypes.c_int64(), ctypes.c_int64()
+        sess._check(sess._lib.ngsep_fetch_coverage(sess._ctx, a, u, ctypes.byref(hi), ctypes.byref(hu)))
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "coverage_counts.npy"), np.array(a[:] + [hi.value], dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "coverage_counts_unique.npy"), np.array(u[:] + [hu.value], dtype=np.float64))
     sess.release_staged()
     sess.close()
     k_ms = sum(ks) / len(ks)
@@ -378,9 +470,14 @@ def main():
     ap.add_argument("--config", default="chr20", choices=["chr20", "yeast", "wgs", "multisample", "coverage"],
                     help="default: chr20 (configs[2]) per GPU at every --gpus N (weak scaling); wgs: configs[3] split "
                          "over the GPUs (strong)")
-    ap.add_argument("--no-cold", action="store_true", help="skip the cache-flushed passes")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the BAM -> VCF end-to-end run")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, the legs that are runs of their own: the CPU baseline, the cache-flushed "
+                         "passes, the BAM -> VCF end-to-end runs (at --gpus N > 1 the sharded one too)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step handed back (the fetched records) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cold", action="store_true", help="--full: skip the cache-flushed passes")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the BAM -> VCF end-to-end run")
     ap.add_argument("--cpu-trunc", type=int, default=2_000_000, help="bp per CPU-baseline piece")
     ap.add_argument("--samples", type=int, default=200)
     ap.add_argument("--contig-first", type=int, default=3, help="multisample: first yeast contig of the shard")
@@ -390,8 +487,12 @@ def main():
                          "--wgs-shard picks the shard this GPU calls (one GPU's part of the 8-GPU split)")
     ap.add_argument("--wgs-shard", type=int, default=-1, help="wgs: the shard to call (default: the rank)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.config == "multisample" and args.depth == 30.0:
         args.depth = 10.0
+    if not args.full:      # a plain run: the timed steps only
+        args.no_cold = args.no_cpu_baseline = args.no_e2e = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -617,6 +718,8 @@ def main():
     st = sessions[0].stats()
     log(f"[rank {rank}] tile {st.tile_positions} positions (max {st.tile_rows_max} rows), pile {st.pile_bytes} B, "
         f"{st.candidates} candidates, {st.hard_sites} needed the exact tally + posterior, {sites_called} calls")
+    if args.dump_outputs:
+        dump_outputs(sessions, multi, args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"))
     cold = cold_passes(sessions[0]) if world == 1 and not args.no_cold and len(sessions) == 1 else None
     stats_all = [s.stats() for s in sessions]
     pile_bytes = sum(x.pile_bytes for x in stats_all)
