@@ -33,7 +33,7 @@ extern "C" {
 #define NGSEP_E_IO (-2)           /* file cannot be read or written */
 #define NGSEP_E_FORMAT (-3)       /* malformed BAM / FASTA */
 #define NGSEP_E_DEVICE (-4)       /* HIP runtime error or no device */
-#define NGSEP_E_UNSUPPORTED (-5)  /* input outside the implemented path (ploidy > 128, > 255 samples, ...) */
+#define NGSEP_E_UNSUPPORTED (-5)  /* input outside the implemented path (ploidy > 128, > 32767 samples, ...) */
 #define NGSEP_E_NOMEM (-6)
 
 typedef struct ngsep_ctx ngsep_ctx;

@@ -18,6 +18,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -582,7 +583,13 @@ extern "C" int ngsep_bam_open(ngsep_ctx* c, const char* path, ngsep_bam** out) {
     b->ctx = c;
     b->path = path;
     b->f = std::fopen(path, "rb");
-    if (!b->f) { delete b; return set_error(c, NGSEP_E_IO, std::string("cannot open ") + path); }
+    if (!b->f) {
+        const int e = errno;                               // (kept for the caller: a population's opens report it)
+        delete b;
+        const int r = set_error(c, NGSEP_E_IO, std::string("cannot open ") + path + ": " + std::strerror(e));
+        errno = e;
+        return r;
+    }
     // single-sample readers inflate on the device, one reader of the context at a time (a population's hundreds of
     // open readers stay on the host threads)
     b->gpu_inflate = gpu_inflate_wanted(c) && !c->gz_busy.exchange(true);
@@ -1582,11 +1589,12 @@ extern "C" int ngsep_call_population_bams(ngsep_ctx* c, const char* const* bam_p
     std::unordered_map<std::string, int32_t> rg_global;
     // the files are opened (header read, decoder started) on all host threads; errors reported in file order
     {
-        std::vector<int> orc((size_t)n_files, NGSEP_OK);
+        std::vector<int> orc((size_t)n_files, NGSEP_OK), oerr((size_t)n_files, 0);
         ngsep::parallel_for(n_files, 1, [&](int64_t lo, int64_t hi) {
             for (int64_t f = lo; f < hi; f++) {
                 ngsep_bam* b = nullptr;
                 int r = ngsep_bam_open(c, bam_paths[f], &b);
+                if (r == NGSEP_E_IO && !b) oerr[(size_t)f] = errno;
                 if (r == NGSEP_OK && c->params.query_seq[0]) {   // -querySeq: every file read from the region's index chunks
                     r = ngsep_bam_set_region(b, c->params.query_seq, std::max<int64_t>(1, c->params.query_first), c->params.query_last);
                     if (r == NGSEP_E_IO) r = NGSEP_OK;
@@ -1601,7 +1609,14 @@ extern "C" int ngsep_call_population_bams(ngsep_ctx* c, const char* const* bam_p
                 close_all();
                 ngsep_bam* b = nullptr;
                 const int r = ngsep_bam_open(c, bam_paths[f], &b);
-                if (r == NGSEP_OK) ngsep_bam_close(b);
+                if (r == NGSEP_OK) {
+                    // it opens alone: the failure came from every file being open at once (hundreds of sample files
+                    // against the process's descriptor limit) -- the system's message of the failed open
+                    ngsep_bam_close(b);
+                    if (orc[(size_t)f] == NGSEP_E_IO && oerr[(size_t)f])
+                        set_error(c, NGSEP_E_IO, std::string("cannot open ") + bam_paths[f] + ": " + std::strerror(oerr[(size_t)f]) +
+                                                     " (" + std::to_string(n_files) + " files are open at once)");
+                }
                 return orc[(size_t)f];
             }
     }

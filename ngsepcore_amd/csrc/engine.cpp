@@ -1969,45 +1969,51 @@ static int build_pop_rg_layout(Staged& s, LayoutArena& arena) {
     const int32_t* R = s.h_reads.data();
     const int64_t* rptr = s.h_rdev.data();            // each read's projected bytes: their offset in the uploaded chunks
     const uint8_t* ref = s.h_ref.data();
-    // stream keys: sample * 128 + read-group rank; the reads of no sample: S * 128
+    // stream keys: sample * 128 + read-group rank; the reads of no sample: S * 128 (16-bit keys while they fit: up to
+    // 511 samples; 32-bit past that)
     const int64_t nkeys = (int64_t)(S + 1) * 128;
-    RawVec<uint16_t> key((size_t)n);
-    parallel_for(n, 1 << 16, [&](int64_t a, int64_t b) {
-        for (int64_t r = a; r < b; r++) {
-            const int sm = (R[r * 4 + 3] >> 8) - 1;
-            key[(size_t)r] = sm < 0 || sm >= S ? (uint16_t)(S * 128) : (uint16_t)(sm * 128 + ((R[r * 4 + 3] >> 1) & 127));
-        }
-    });
-    // a stable counting sort by key: per-chunk histograms, (key, chunk) offsets, scatter
-    const int64_t nch = std::max<int64_t>(1, std::min<int64_t>(64, n / 65536 + 1)), chl = (n + nch - 1) / nch;
-    std::vector<int64_t> hist((size_t)(nch * nkeys), 0);
-    parallel_for(nch, 1, [&](int64_t a, int64_t b) {
-        for (int64_t c = a; c < b; c++) {
-            int64_t* h = &hist[(size_t)(c * nkeys)];
-            for (int64_t r = c * chl; r < std::min(n, (c + 1) * chl); r++) h[key[(size_t)r]]++;
-        }
-    });
+    // a stable counting sort by key: per-chunk histograms, (key, chunk) offsets, scatter.  The histograms are
+    // chunks x keys entries: fewer chunks for a large population, so that they stay within 2^23 entries (64 MB)
+    const int64_t nch = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(64, n / 65536 + 1), ((int64_t)1 << 23) / nkeys));
+    const int64_t chl = (n + nch - 1) / nch;
     std::vector<int64_t> kcount((size_t)nkeys, 0);
-    {
-        int64_t run = 0;
-        for (int64_t k = 0; k < nkeys; k++)
-            for (int64_t c = 0; c < nch; c++) {
-                int64_t& h = hist[(size_t)(c * nkeys + k)];
-                const int64_t v = h;
-                h = run;
-                run += v;
-                kcount[(size_t)k] += v;
-            }
-    }
     RawVec<int32_t> ord((size_t)n);
-    parallel_for(nch, 1, [&](int64_t a, int64_t b) {
-        for (int64_t c = a; c < b; c++) {
-            int64_t* h = &hist[(size_t)(c * nkeys)];
-            for (int64_t r = c * chl; r < std::min(n, (c + 1) * chl); r++) ord[(size_t)h[key[(size_t)r]]++] = (int32_t)r;
+    auto sort_by_key = [&](auto key_type) {
+        using K = decltype(key_type);
+        RawVec<K> key((size_t)n);
+        parallel_for(n, 1 << 16, [&](int64_t a, int64_t b) {
+            for (int64_t r = a; r < b; r++) {
+                const int sm = (R[r * 4 + 3] >> 8) - 1;
+                key[(size_t)r] = sm < 0 || sm >= S ? (K)(S * 128) : (K)(sm * 128 + ((R[r * 4 + 3] >> 1) & 127));
+            }
+        });
+        std::vector<int64_t> hist((size_t)(nch * nkeys), 0);
+        parallel_for(nch, 1, [&](int64_t a, int64_t b) {
+            for (int64_t c = a; c < b; c++) {
+                int64_t* h = &hist[(size_t)(c * nkeys)];
+                for (int64_t r = c * chl; r < std::min(n, (c + 1) * chl); r++) h[key[(size_t)r]]++;
+            }
+        });
+        {
+            int64_t run = 0;
+            for (int64_t k = 0; k < nkeys; k++)
+                for (int64_t c = 0; c < nch; c++) {
+                    int64_t& h = hist[(size_t)(c * nkeys + k)];
+                    const int64_t v = h;
+                    h = run;
+                    run += v;
+                    kcount[(size_t)k] += v;
+                }
         }
-    });
-    decltype(key)().swap(key);
-    std::vector<int64_t>().swap(hist);
+        parallel_for(nch, 1, [&](int64_t a, int64_t b) {
+            for (int64_t c = a; c < b; c++) {
+                int64_t* h = &hist[(size_t)(c * nkeys)];
+                for (int64_t r = c * chl; r < std::min(n, (c + 1) * chl); r++) ord[(size_t)h[key[(size_t)r]]++] = (int32_t)r;
+            }
+        });
+    };
+    if (nkeys <= 65536) sort_by_key(uint16_t{});
+    else sort_by_key(uint32_t{});
     // streams (non-empty keys in key order), their entries padded to whole groups
     std::vector<int64_t> st_r0, st_n, st_e0;          // first read (in ord), reads, first entry
     s.h_samp_st.assign((size_t)S + 2, 0);
@@ -4027,7 +4033,7 @@ extern "C" int ngsep_set_samples(ngsep_ctx* c, int32_t n_samples, const char* co
     if (!c || n_samples < 0 || n_read_groups < 0 || (n_samples && !sample_ids) || (n_read_groups && (!rg_sample || !rg_rank)))
         return set_error(c, NGSEP_E_INVALID, "bad sample description");
     if (n_samples > kMaxSamplesDevice)
-        return set_error(c, NGSEP_E_UNSUPPORTED, "more than " + std::to_string(kMaxSamplesDevice) + " samples per device run");
+        return set_error(c, NGSEP_E_UNSUPPORTED, "more than " + std::to_string(kMaxSamplesDevice) + " samples (the reads' 16-bit sample index)");
     c->sample_ids.clear();
     for (int32_t i = 0; i < n_samples; i++) c->sample_ids.emplace_back(sample_ids[i] ? sample_ids[i] : "");
     c->rg_sample.assign(rg_sample, rg_sample + n_read_groups);

@@ -101,7 +101,9 @@ inline int site_alt(const R& s) {
 static_assert(sizeof(ngsep_site_out) == 152, "site record layout");
 static_assert(sizeof(ngsep_sample_call) == 76, "sample call layout");
 static_assert(sizeof(ngsep_popsite_out) == 20, "population site layout");
-constexpr int kMaxSamplesDevice = 255;     // samples genotyped by one workgroup (one thread each, one for reads of no sample)
+constexpr int kMaxSamplesDevice = 32767;   // samples of one run: Staged::sample / RawRead::sample are int16_t (KPM's threads take the sample
+                                           // columns in blocks of 256 past 255 samples, kernels.hip k_posterior_wide)
+constexpr int kPopNarrowSamples = 255;     // ... up to here one KPM thread per column and 256-bit first-stage masks
 
 // Likelihood addends for the SNV model with n=4 alleles and f=g=250
 // (CountsHelper.java:147-185 with heterozygousProportion 0.5, SingleSampleVariantPileupListener.java:236)

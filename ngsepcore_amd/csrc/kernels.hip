@@ -98,8 +98,9 @@ struct RunSlot {                     // one in-flight single-sample run (see dev
 };
 
 // KPM's two stages (k_stage_a, then k_posterior_multi over its queue): KLM's (position, sample) pairs of the columns it could not prove hom-ref,
-// in kKlShards segments of pseg; KQN's queue index of every need word's first bit; per queued position a 256-bit sample
-// mask (zeroed once: the first stage clears what it read); the second stage's queue
+// in kKlShards segments of pseg; KQN's queue index of every need word's first bit; per queued position a sample mask of
+// mwords words (8 up to kPopNarrowSamples samples, else a bit per sample; zeroed once: the first stage clears what it
+// read); the second stage's queue
 struct PopStage {
     uint2* pairs = nullptr;
     int64_t pseg = 0;
@@ -108,12 +109,14 @@ struct PopStage {
     uint32_t* pmask = nullptr;
     QueueSite* qB = nullptr;
     int64_t cap = 0;                         // queue entries of pmask and qB
+    int32_t mwords = 8;                      // mask words per queue entry
     void release() {
         (void)hipFree(pairs); (void)hipFree(qword); (void)hipFree(pmask); (void)hipFree(qB);
         pairs = nullptr; qword = nullptr; pmask = nullptr; qB = nullptr;
         pseg = cap_qword = cap = 0;
     }
-    hipError_t ensure(int64_t qcap, int64_t nwords, hipStream_t st);   // for a queue of qcap positions over nwords words
+    // for a queue of qcap positions over nwords need words, n_samples samples
+    hipError_t ensure(int64_t qcap, int64_t nwords, int32_t n_samples, hipStream_t st);
 };
 
 struct MultiSlot {                   // one in-flight multisample run (device_submit_multi / device_collect_multi)
@@ -190,6 +193,8 @@ struct Device {
     uint8_t* d_deep_flag = nullptr;  //   ... as a byte per tile (k_scan_pop<true> skips them)
     uint8_t* d_gcol = nullptr;       //   KPM / k_stage_a columns when they do not fit LDS (kPopGatherCap)
     size_t cap_gcol = 0;
+    uint8_t* d_wstate = nullptr;     //   more than kPopNarrowSamples samples: KPM's per-column state (k_posterior_wide)
+    size_t cap_wstate = 0;
     uint32_t* d_need = nullptr;      //   open positions, a bit per global position
     bool need_clean = false;         //   d_need is all zero (cleared by the last run's k_stage_a)
     PopStage pstage;                 //   KPM's two stages (device_run_multi)
@@ -2006,9 +2011,12 @@ __global__ __launch_bounds__(kKlmThreads) __attribute__((amdgpu_waves_per_eu(8))
 // KPM's first stage, its per-position sample masks: pair (position, sample) -> bit sample of the position's queue entry
 // (KQN's word bases: qword[w] = the queue index of word w's first open position).  A segment past its capacity sets
 // counters[3] bit 62: the first stage then passes every position to the second.
+// WIDE (more than kPopNarrowSamples samples): mwords = ceil(S / 32) mask words per queue entry, else 8.
+template <bool WIDE>
 __global__ __launch_bounds__(256) void k_pair_mask(const uint2* __restrict__ pairs, int64_t pseg, const uint32_t* __restrict__ need,
                                                    const int32_t* __restrict__ qword, uint32_t* __restrict__ pmask, int64_t qcap,
-                                                   unsigned long long* __restrict__ counters) {
+                                                   unsigned long long* __restrict__ counters, int32_t mwords) {
+    const int64_t mw = WIDE ? (int64_t)mwords : 8;
     const int sh = (int)blockIdx.y;
     const unsigned long long n = counters[kCtrShard0 + kCtrShardStride * sh + 2];
     if ((int64_t)n > pseg) {
@@ -2019,7 +2027,7 @@ __global__ __launch_bounds__(256) void k_pair_mask(const uint2* __restrict__ pai
         const uint2 pr = pairs[(int64_t)sh * pseg + k];
         const uint32_t gpos = pr.x, w = gpos >> 5;
         const int64_t q = (int64_t)qword[w] + __popc(need[w] & ((1u << (gpos & 31)) - 1u));
-        if (q < qcap) atomicOr(&pmask[q * 8 + (pr.y >> 5)], 1u << (pr.y & 31));
+        if (q < qcap && (!WIDE || (int64_t)(pr.y >> 5) < mw)) atomicOr(&pmask[q * mw + (pr.y >> 5)], 1u << (pr.y & 31));
     }
 }
 
@@ -2036,7 +2044,7 @@ __global__ __launch_bounds__(256) void k_pair_mask(const uint2* __restrict__ pai
 constexpr int kPopThreads = 256;
 constexpr int kPopTileLog2 = 7;
 static_assert((1 << kPopTileLog2) == kPopTile, "KPM pile tile");
-static_assert(kPopThreads >= kMaxSamplesDevice, "one thread per sample");
+static_assert(kPopThreads > kPopNarrowSamples, "k_posterior_multi: one thread per column (more samples: k_posterior_wide)");
 
 struct PopCall {
     int kind, n_called, c0, c1, gq, total_cn;
@@ -2384,12 +2392,14 @@ __device__ __forceinline__ int nth_set_bit(uint32_t w, int r) {   // the r-th (0
     return __builtin_ctz(w);
 }
 // GCOL: the lanes' columns in pg.gcol (blockIdx.x's 64 x stride bytes) -- a population too deep for them in LDS
-template <bool GCOL>
+// WIDE: more than kPopNarrowSamples samples -- a queue entry's mask is mwords = ceil(S / 32) words, scanned 64 words at a
+// time (still at most 64 masked samples genotyped, one per lane; more go to the second stage)
+template <bool GCOL, bool WIDE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_stage_a(
     const QueueSite* __restrict__ queue, const unsigned long long* qn, int64_t qcap, const PopGather pg,
     const LikTables* __restrict__ tabs, GenotypeParams gp, int32_t ploidy, uint32_t* __restrict__ pmask,
     QueueSite* __restrict__ qB, unsigned long long* __restrict__ qB_n, int64_t qB_cap, unsigned long long* counters,
-    uint32_t* __restrict__ need_clear, int64_t need_words) {
+    uint32_t* __restrict__ need_clear, int64_t need_words, int32_t mwords) {
     __shared__ double s_t[3][32];
     __shared__ double s_L[10][64];
     // the pass's open-position bits are read for the last time by k_pair_mask, before this kernel: cleared here for the
@@ -2410,23 +2420,50 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_
     };
     for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
         const QueueSite qs = queue[i];
-        const uint32_t mw = lane < 8 ? pmask[i * 8 + lane] : 0u;
-        if (lane < 8) pmask[i * 8 + lane] = 0u;          // (cleared for the next pass)
-        if (passall) { pass_on(qs); continue; }
-        uint32_t incl = (uint32_t)__popc(mw);
-#pragma unroll
-        for (int o = 1; o < 8; o <<= 1) {
-            const uint32_t x = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += x;
-        }
-        const uint32_t nmask = (uint32_t)__shfl((int)incl, 7, 64);
-        if (nmask > 64u) { pass_on(qs); continue; }
         int s = -1;
+        if constexpr (WIDE) {
+            // the entry's words 64 at a time: lane j takes the j-th set bit over all of them (off: the bits of the chunks
+            // before); every word is cleared for the next pass whatever becomes of the position
+            uint32_t off = 0;
+            for (int32_t base = 0; base < mwords; base += 64) {
+                const bool in = base + lane < mwords;
+                const uint32_t mw = in ? pmask[i * mwords + base + lane] : 0u;
+                if (in) pmask[i * mwords + base + lane] = 0u;
+                uint32_t incl = (uint32_t)__popc(mw);
 #pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const uint32_t wk = (uint32_t)__shfl((int)mw, k, 64), ik = (uint32_t)__shfl((int)incl, k, 64);
-            const uint32_t ek = ik - (uint32_t)__popc(wk);
-            if ((uint32_t)lane >= ek && (uint32_t)lane < ik) s = 32 * k + nth_set_bit(wk, lane - (int)ek);
+                for (int o = 1; o < 64; o <<= 1) {
+                    const uint32_t x = __shfl_up(incl, o, 64);
+                    if (lane >= o) incl += x;
+                }
+                if (off < 64u && !passall) {
+                    for (unsigned long long nz = __ballot(mw != 0u); nz; nz &= nz - 1ull) {   // (wave-uniform)
+                        const int k = __builtin_ctzll(nz);
+                        const uint32_t wk = (uint32_t)__shfl((int)mw, k, 64), ik = off + (uint32_t)__shfl((int)incl, k, 64);
+                        const uint32_t ek = ik - (uint32_t)__popc(wk);
+                        if ((uint32_t)lane >= ek && (uint32_t)lane < ik) s = 32 * (base + k) + nth_set_bit(wk, lane - (int)ek);
+                    }
+                }
+                off += (uint32_t)__shfl((int)incl, 63, 64);
+            }
+            if (passall || off > 64u) { pass_on(qs); continue; }
+        } else {
+            const uint32_t mw = lane < 8 ? pmask[i * 8 + lane] : 0u;
+            if (lane < 8) pmask[i * 8 + lane] = 0u;          // (cleared for the next pass)
+            if (passall) { pass_on(qs); continue; }
+            uint32_t incl = (uint32_t)__popc(mw);
+#pragma unroll
+            for (int o = 1; o < 8; o <<= 1) {
+                const uint32_t x = __shfl_up(incl, o, 64);
+                if (lane >= o) incl += x;
+            }
+            const uint32_t nmask = (uint32_t)__shfl((int)incl, 7, 64);
+            if (nmask > 64u) { pass_on(qs); continue; }
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const uint32_t wk = (uint32_t)__shfl((int)mw, k, 64), ik = (uint32_t)__shfl((int)incl, k, 64);
+                const uint32_t ek = ik - (uint32_t)__popc(wk);
+                if ((uint32_t)lane >= ek && (uint32_t)lane < ik) s = 32 * k + nth_set_bit(wk, lane - (int)ek);
+            }
         }
         const int32_t gpos = qs.gpos;
         const uint32_t rc = (uint32_t)qs.rc;
@@ -2728,6 +2765,250 @@ __global__ __launch_bounds__(kPopThreads) __attribute__((amdgpu_waves_per_eu(WPE
             // 4-wave build into scratch)
             uint32_t* o = reinterpret_cast<uint32_t*>(calls + (int64_t)at * n_samples + tid);
             static_assert(sizeof(ngsep_sample_call) == 76, "ngsep_sample_call: 19 dwords");
+            o[0] = (uint32_t)(uint8_t)call.kind | (uint32_t)(uint8_t)call.n_called << 8 | (uint32_t)(uint8_t)call.c0 << 16 |
+                   (uint32_t)(uint8_t)call.c1 << 24;
+            o[1] = (uint32_t)(uint16_t)call.gq | (uint32_t)(uint16_t)call.total_cn << 16;
+            o[2] = (uint32_t)(pool ? pr.dp : total);
+#pragma unroll
+            for (int k = 0; k < 4; k++) o[3 + k] = (uint32_t)cnt[k];
+            o[7] = (uint32_t)call.acnp;                              // (int16 acn[0], acn[1])
+            o[8] = (uint32_t)(call.acnp >> 32);                      // (acn[2], acn[3])
+            uint32_t* pl = o + 9;
+            int npl = 0;                                           // PL values written (the rest are 0)
+            // PL (VCFFileWriter.java:200-212) from the call report
+            if (pool) {
+                if (pr.report) {
+                    for (int j = 0; j < nal; j++)
+                        for (int ii = 0; ii <= j; ii++)
+                            pl[npl++] = (uint32_t)(int32_t)java_round_d(-10 * sel10(pr.L, ii * nal - ii * (ii - 1) / 2 + (j - ii)));
+                }
+            } else if (call.kind == 0) {
+                const float hr = (float)sel10(Lr, tri_d(idx[0], idx[0])), ha = (float)sel10(Lr, tri_d(idx[1], idx[1]));
+                const float ra = (float)sel10(Lr, tri_d(idx[0], idx[1])), ar = ra;
+                const bool present = (hr + ra + ar + ha) != 0;     // CalledSNV.java:422 (float sum)
+                if (present) {
+                    pl[0] = (uint32_t)(int32_t)java_round_d(-10 * (double)hr);
+                    pl[1] = (uint32_t)(int32_t)java_round_d(-10 * (double)ra);
+                    pl[2] = (uint32_t)(int32_t)java_round_d(-10 * (double)ha);
+                    npl = 3;
+                }
+            } else if (total > 0) {
+                for (int j = 0; j < nal; j++)
+                    for (int ii = 0; ii <= j; ii++)
+                        pl[npl++] = (uint32_t)(int32_t)java_round_d(-10 * sel10(Lr, tri_d(sel4i(idx, ii), sel4i(idx, j))));
+            }
+            for (int k = npl; k < 10; k++) pl[k] = 0u;
+        }
+    }
+}
+
+// KPM for more than kPopNarrowSamples samples: thread t takes the columns t, t + 256, ... up to column S (the reads of no
+// sample), one after the other.  A column is still walked by one thread in rank order, then pending order, and its ten
+// log-conditionals summed by that thread in that order: the fp64 results are k_posterior_multi's.  What a column keeps
+// between the phases -- counts, total, rows, log-conditionals: kPopWideState bytes -- lives in a device scratch, a part per
+// workgroup (wstate, column-major over the S + 1 columns: a thread only ever reads what it wrote itself, so no fence);
+// the columns themselves are always gathered into pg.gcol (GATHER 1).  The block reductions (pooled counts, called
+// alleles, QS) add a thread's columns up before its one LDS atomic.  A sample's call is not kept across the
+// multi-allelic loop: the emission genotypes it again for the final allele set (the same function of the same state).
+constexpr int kPopWideState = 10 * 8 + 6 * 4;
+template <bool POOL, int GATHER>
+__global__ __launch_bounds__(kPopThreads) __attribute__((amdgpu_waves_per_eu(2))) void k_posterior_wide(
+    const QueueSite* __restrict__ queue, const unsigned long long* qn, int64_t qcap,
+    const uint8_t* __restrict__ ppile, const int32_t* __restrict__ prow, const int64_t* __restrict__ pboff,
+    const PopGather pg, const LikTables* __restrict__ tabs, GenotypeParams gp,
+    int32_t n_samples, double min_adf, int32_t ploidy, const PoolTables* __restrict__ pt,
+    ngsep_popsite_out* __restrict__ sites, ngsep_sample_call* __restrict__ calls,
+    unsigned long long* counters, int64_t cap, uint8_t* __restrict__ wstate) {
+    __shared__ double s_t[3][32];
+    __shared__ double s_L[10][kPopThreads];             // the column in hand: its log-conditionals (LdsRow)
+    __shared__ int32_t s_pc[4], s_tot;
+    __shared__ int32_t s_called, s_qs;
+    __shared__ unsigned long long s_base;
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid < 96) s_t[tid >> 5][tid & 31] = (tid < 32 ? tabs->A : tid < 64 ? tabs->H : tabs->E)[tid & 31];
+    int64_t n = (int64_t)*qn;
+    if (n > qcap) n = qcap;
+    constexpr bool pool = POOL;
+    const int64_t ncol = (int64_t)n_samples + 1;
+    double* const wL = reinterpret_cast<double*>(wstate + (int64_t)blockIdx.x * ncol * kPopWideState);   // [10][ncol]
+    int32_t* const wI = reinterpret_cast<int32_t*>(wL + 10 * ncol);                                     // [6][ncol]
+    // column c of a queued position (as k_posterior_multi's column_of / its GCOL part)
+    auto column_of = [&](int32_t gpos, int c, int32_t& rows) -> const uint8_t* {
+        if (GATHER == 1) return pg.gcol + ((int64_t)blockIdx.x * ncol + c) * pg.stride;
+        const int64_t b0 = (int64_t)(gpos >> kPopTileLog2) * ncol, bi = b0 + c;
+        const int64_t stride = (pboff[b0 + ncol] - pboff[b0]) >> kPopTileLog2;
+        rows = prow[bi];
+        return ppile + pboff[bi] + (int64_t)(gpos & (kPopTile - 1)) * stride;
+    };
+    const LdsRow Lr{&s_L[0][tid]};
+    // sample c genotyped for the alleles idx[0..nal) from its kept state (genotypeVariantSample, as k_posterior_multi)
+    auto genotype_column = [&](int32_t gpos, int c, int nal, const int* idx, int* cnt, int& total, PoolResult& pr) -> PopCall {
+        PopCall call;
+        cnt[0] = wI[c]; cnt[1] = wI[ncol + c]; cnt[2] = wI[2 * ncol + c]; cnt[3] = wI[3 * ncol + c];
+        total = wI[4 * ncol + c];
+        if (pool) {
+            int32_t rows = wI[5 * ncol + c];
+            const uint8_t* col = column_of(gpos, c, rows);
+            pr = pool_genotype(col, rows, total, cnt, idx, nal, pt, gp.max_q);
+            call.kind = 1; call.n_called = pr.n_called; call.c0 = pr.c0 < 0 ? 0 : pr.c0; call.c1 = pr.c1 < 0 ? 0 : pr.c1;
+            call.gq = pr.gq; call.total_cn = ploidy;
+            call.clear_acn();
+            call.set_acn(0, pr.acn[0]); call.set_acn(1, pr.acn[1]); call.set_acn(2, pr.acn[2]); call.set_acn(3, pr.acn[3]);
+            if (40 > call.gq) {
+                call.n_called = 0; call.gq = 0;
+                call.clear_acn();
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 10; k++) s_L[k][tid] = wL[k * ncol + c];
+            __atomic_signal_fence(__ATOMIC_SEQ_CST);
+            call = genotype_sample_d(Lr, cnt, total, nal, idx, gp, ploidy);
+        }
+        return call;
+    };
+    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
+        __syncthreads();
+        const QueueSite qs = queue[i];
+        const int32_t gpos = qs.gpos;
+        const uint32_t rc = (uint32_t)qs.rc;
+        if (tid == 0) { s_pc[0] = s_pc[1] = s_pc[2] = s_pc[3] = 0; s_tot = 0; s_called = 0; s_qs = 0; }
+        __syncthreads();
+        // 1-3. every column gathered and tallied (k_posterior_multi's walk), its state kept, the thread's part of the
+        //      pooled counts summed
+        {
+            int c0 = 0, c1 = 0, c2 = 0, c3 = 0, tt = 0;
+            for (int c = tid; c <= n_samples; c += kPopThreads) {
+                int total = 0;
+                int cnt[4] = {0, 0, 0, 0};
+                double L[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                int32_t rows = 0;
+                const uint8_t* col = column_of(gpos, c, rows);
+                if (GATHER == 1) {
+                    rows = pop_gather<NGSEP_KPM_GBATCH>(pg, gpos, c, const_cast<uint8_t*>(col), pg.stride);
+                    if (rows > pg.stride) {                      // (the host's coverage bound makes this unreachable)
+                        atomicOr(&counters[3], 1ull << 63);
+                        rows = pg.stride;
+                    }
+                }
+                const bool tally = c < n_samples && !pool;      // (the pool algorithm walks the column itself)
+                for (int32_t r0 = 0; r0 < rows; r0 += 8) {
+                    uint32_t code[8];
+#pragma unroll
+                    for (int k = 0; k < 8; k++) code[k] = r0 + k < rows ? (uint32_t)col[r0 + k] : 0u;
+#pragma unroll
+                    for (int k = 0; k < 8; k++) {
+                        const uint32_t cd = code[k];
+                        total += cd != 0;                                  // CountsHelper.java:210
+                        if (!(cd & 0x80u)) continue;                       // q<=3 or not A/C/G/T (:214-221)
+                        const uint32_t a = (cd >> 5) & 3u;
+                        cnt[0] += a == 0; cnt[1] += a == 1; cnt[2] += a == 2; cnt[3] += a == 3;
+                        if (!tally) continue;
+                        int q = (int)(cd & 31u);
+                        q = q > gp.max_q ? gp.max_q : q;                   // -maxBaseQS (:217-219)
+                        const double A = s_t[0][q], H = s_t[1][q], E = s_t[2][q];
+                        L[0] += a == 0 ? A : E;
+                        L[4] += a == 1 ? A : E;
+                        L[7] += a == 2 ? A : E;
+                        L[9] += a == 3 ? A : E;
+                        L[1] += a <= 1 ? H : E;
+                        L[2] += (a & 1) == 0 ? H : E;
+                        L[3] += (a == 0 || a == 3) ? H : E;
+                        L[5] += (a == 1 || a == 2) ? H : E;
+                        L[6] += (a & 1) == 1 ? H : E;
+                        L[8] += a >= 2 ? H : E;
+                    }
+                }
+                c0 += cnt[0]; c1 += cnt[1]; c2 += cnt[2]; c3 += cnt[3]; tt += total;
+                if (c < n_samples) {
+                    if (!pool) {
+#pragma unroll
+                        for (int k = 0; k < 10; k++) wL[k * ncol + c] = L[k];
+                    }
+                    wI[c] = cnt[0]; wI[ncol + c] = cnt[1]; wI[2 * ncol + c] = cnt[2]; wI[3 * ncol + c] = cnt[3];
+                    wI[4 * ncol + c] = total;
+                    wI[5 * ncol + c] = rows;
+                }
+            }
+            for (int o = 32; o > 0; o >>= 1) {
+                c0 += __shfl_xor(c0, o, 64); c1 += __shfl_xor(c1, o, 64);
+                c2 += __shfl_xor(c2, o, 64); c3 += __shfl_xor(c3, o, 64);
+                tt += __shfl_xor(tt, o, 64);
+            }
+            if (lane == 0) {
+                atomicAdd(&s_pc[0], c0); atomicAdd(&s_pc[1], c1); atomicAdd(&s_pc[2], c2); atomicAdd(&s_pc[3], c3);
+                atomicAdd(&s_tot, tt);
+            }
+        }
+        __syncthreads();
+        const bool known = (rc & 0x400u) != 0;                     // -knownVariants (as k_posterior_multi)
+        if (s_tot == 0 && !known) continue;                       // createSNVVariantPool: totalCount 0
+        if (ABLATE(gp.ablate, 64)) continue;                             // diagnostics: tallies only
+        // 4. candidate alleles from the pooled counts (createSNVVariantPool)
+        if (!(rc & 0x80u)) continue;                               // N (or masked) reference: no variant
+        const int refIdx = (int)((rc >> 5) & 3u);
+        const int pc[4] = {s_pc[0], s_pc[1], s_pc[2], s_pc[3]};
+        const int sum = pc[0] + pc[1] + pc[2] + pc[3];
+        double minCount = min_adf * sum;
+        if (minCount < 1) minCount = 1;
+        int idx[4] = {refIdx, 0, 0, 0};
+        int nal = 1;
+        if (known) {
+            idx[1] = (int)((rc >> 8) & 3u);
+            nal = 2;
+        } else {
+            for (int a = 0; a < 4; a++)
+                if (a != refIdx && pc[a] >= minCount) { set4i(idx, nal < 4 ? nal : 3, a); nal++; }
+        }
+        if (nal < 2) continue;
+        int multisnv = nal > 2;
+        // 5. genotype every sample; shrink a multi-allelic variant to the called alleles
+        int qsv = 0;
+        for (;;) {
+            if (tid == 0) { s_called = 0; s_qs = 0; }
+            __syncthreads();
+            int q = 0, bits = 0;
+            for (int c = tid; c < n_samples; c += kPopThreads) {
+                int cnt[4], total;
+                PoolResult pr;
+                const PopCall call = genotype_column(gpos, c, nal, idx, cnt, total, pr);
+                const bool homref = call.n_called == 1 && call.c0 == 0;
+                if (call.n_called > 0 && !homref) q = max(q, call.gq);
+                if (call.n_called >= 1) bits |= 1 << sel4i(idx, call.c0 & 3);
+                if (call.n_called == 2) bits |= 1 << sel4i(idx, call.c1 & 3);
+            }
+            if (q) atomicMax(&s_qs, q);
+            if (bits) atomicOr(&s_called, bits);
+            __syncthreads();
+            qsv = s_qs;
+            const int set = s_called | (1 << refIdx);
+            __syncthreads();                                       // everyone has read before the next reset
+            if (nal <= 2) break;
+            if (__popc(set) == nal) break;
+            nal = 1;
+            for (int a = 0; a < 4; a++) if (a != refIdx && (set >> a & 1)) { set4i(idx, nal, a); nal++; }
+            multisnv = 0;                                          // makeNewVariant: SNV or GenomicVariantImpl (no TYPE)
+            if (nal < 2) break;
+        }
+        if (nal < 2) continue;                                     // only the reference allele is left
+        if (!known && (qsv == 0 || qsv < gp.min_quality)) continue;   // MultisampleVariantsDetector.java:534
+        // 6. emit the site and its calls
+        __syncthreads();
+        if (tid == 0) s_base = atomicAdd(&counters[0], 1ull);
+        __syncthreads();
+        const unsigned long long at = s_base;
+        if ((int64_t)at >= cap) continue;
+        if (tid == 0) {
+            ngsep_popsite_out o;
+            o.seq_id = (int32_t)i; o.pos = gpos; o.n_alleles = (int8_t)nal;   // (seq_id: the queue index, host order)
+            for (int k = 0; k < 4; k++) o.alleles[k] = (int8_t)(k < nal ? idx[k] : -1);
+            o.multisnv_type = (int8_t)multisnv; o.qual = (int16_t)qsv; o.pad = 0;
+            sites[at] = o;
+        }
+        for (int c = tid; c < n_samples; c += kPopThreads) {
+            int cnt[4], total;
+            PoolResult pr;
+            const PopCall call = genotype_column(gpos, c, nal, idx, cnt, total, pr);
+            uint32_t* o = reinterpret_cast<uint32_t*>(calls + (int64_t)at * n_samples + c);
             o[0] = (uint32_t)(uint8_t)call.kind | (uint32_t)(uint8_t)call.n_called << 8 | (uint32_t)(uint8_t)call.c0 << 16 |
                    (uint32_t)(uint8_t)call.c1 << 24;
             o[1] = (uint32_t)(uint16_t)call.gq | (uint32_t)(uint16_t)call.total_cn << 16;
@@ -3198,6 +3479,7 @@ void device_destroy(Device* d) {
     (void)hipFree(d->d_psites);
     (void)hipFree(d->d_pcalls);
     (void)hipFree(d->d_gcol);
+    (void)hipFree(d->d_wstate);
     (void)hipFree(d->d_pcalls_ord);
     (void)hipFree(d->d_mforced);
     (void)hipFree(d->d_mforced_ctr);
@@ -3993,12 +4275,20 @@ static auto kpm_kernel(int ploidy, int gather, bool gcol) {
         return ploidy >= 3 ? k_posterior_multi<true, kKpmWavesPerEu, 1, false> : k_posterior_multi<false, kKpmWavesPerEu, 1, false>;
     return ploidy >= 3 ? k_posterior_multi<true, kKpmWavesPerEu, 0, false> : k_posterior_multi<false, kKpmWavesPerEu, 0, false>;
 }
+// more than kPopNarrowSamples samples: the columns in blocks of 256 (k_posterior_wide)
+static auto kpm_wide_kernel(int ploidy, int gather) {
+    if (gather == 1) return ploidy >= 3 ? k_posterior_wide<true, 1> : k_posterior_wide<false, 1>;
+    return ploidy >= 3 ? k_posterior_wide<true, 0> : k_posterior_wide<false, 0>;
+}
 
 // Where KPM's and k_stage_a's gathered columns live: LDS while the bytes of one workgroup's columns ((S + 1) x the
 // per-sample coverage bound for KPM, 64 x it for the first stage) stay within kPopGatherCap, else the device scratch
 // d_gcol, a part per workgroup -- the grid then shrinks so that the scratch stays within kPopGatherCap's budget
 // (kPopGcolBudget).  No depth is refused (MultisampleVariantsDetector genotypes a position at whatever depth it has,
 // :522-558, :674-693).  NGSEP_POP_GCOL=1 (test hook) takes the scratch at any depth.
+// More than kPopNarrowSamples samples (k_posterior_wide): KPM's columns always in the scratch, its per-column state in a
+// second one (d_wstate, kPopWideState bytes per column), both within the budget by the same trim of the grid -- also
+// for the realigner regions' pile (no population layout), where only the state is needed.
 struct PopCols {
     bool kpm_gcol = false, sta_gcol = false;
     unsigned kpm_grid = 1, sta_grid = 1;
@@ -4013,7 +4303,14 @@ static PopCols pop_cols(Device* d, std::string& err, bool* fail) {
     c.sta_gcol = d->prg && (force || sta_wg > kPopGatherCap);
     c.kpm_grid = kpm_grid(d);
     c.sta_grid = sta_grid();
+    const bool wide = d->n_samples > kPopNarrowSamples;
+    const int64_t wst_wg = (int64_t)(d->n_samples + 1) * kPopWideState;
+    if (wide) c.kpm_gcol = d->prg;
     if (c.kpm_gcol) c.kpm_grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(c.kpm_grid, kPopGcolBudget / kpm_wg));
+    if (wide) {
+        c.kpm_grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(c.kpm_grid, kPopGcolBudget / wst_wg));
+        if (ensure_dev(&d->d_wstate, &d->cap_wstate, (size_t)c.kpm_grid * (size_t)wst_wg, false, err)) { *fail = true; return c; }
+    }
     if (c.sta_gcol) c.sta_grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(c.sta_grid, kPopGcolBudget / sta_wg));
     const size_t need = std::max<size_t>(c.kpm_gcol ? (size_t)c.kpm_grid * (size_t)kpm_wg : 0,
                                          c.sta_gcol ? (size_t)c.sta_grid * (size_t)sta_wg : 0);
@@ -4061,20 +4358,25 @@ static hipError_t launch_pop_scan(Device* d, const GenotypeParams& g, uint32_t* 
                           (const uint32_t*)need, (const uint8_t*)d->d_ref, nwords, queue, ctr, qcap, stage ? stage->qword : nullptr);
     if ((e = launch_check()) != hipSuccess) return e;
     if (stage) {                                       // KPM's first stage's sample masks
-        hipLaunchKernelGGL(k_pair_mask, dim3(16, kKlShards), dim3(256), 0, d->stream, (const uint2*)stage->pairs, stage->pseg,
-                           (const uint32_t*)need, (const int32_t*)stage->qword, stage->pmask, qcap, ctr);
+        hipLaunchKernelGGL(d->n_samples > kPopNarrowSamples ? k_pair_mask<true> : k_pair_mask<false>, dim3(16, kKlShards), dim3(256),
+                           0, d->stream, (const uint2*)stage->pairs, stage->pseg, (const uint32_t*)need,
+                           (const int32_t*)stage->qword, stage->pmask, qcap, ctr, stage->mwords);
         e = launch_check();
     }
     return e;
 }
 
-hipError_t PopStage::ensure(int64_t qcap, int64_t nwords, hipStream_t st) {
+static int32_t pop_mask_words(int32_t n_samples) { return n_samples <= kPopNarrowSamples ? 8 : (n_samples + 31) / 32; }
+hipError_t PopStage::ensure(int64_t qcap, int64_t nwords, int32_t n_samples, hipStream_t st) {
     hipError_t e = hipSuccess;
-    if (qcap > cap) {
+    const int32_t mw = pop_mask_words(n_samples);
+    if (qcap > cap || mw != mwords) {
+        qcap = std::max(qcap, cap);
+        mwords = mw;
         (void)hipFree(pmask); (void)hipFree(qB); (void)hipFree(pairs);
         pmask = nullptr; qB = nullptr; pairs = nullptr;
-        if ((e = hipMalloc(&pmask, (size_t)qcap * 8 * sizeof(uint32_t))) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(pmask, 0, (size_t)qcap * 8 * sizeof(uint32_t), st)) != hipSuccess) return e;
+        if ((e = hipMalloc(&pmask, (size_t)qcap * (size_t)mwords * sizeof(uint32_t))) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(pmask, 0, (size_t)qcap * (size_t)mwords * sizeof(uint32_t), st)) != hipSuccess) return e;
         if ((e = hipMalloc(&qB, (size_t)qcap * sizeof(QueueSite))) != hipSuccess) return e;
         pseg = std::max<int64_t>(4096, qcap / 4);           // (segments past this: the first stage passes everything on)
         if ((e = hipMalloc(&pairs, (size_t)pseg * kKlShards * sizeof(uint2))) != hipSuccess) return e;
@@ -4108,10 +4410,13 @@ static PopGather pop_gather_of(const Device* d, bool gcol) {
 static hipError_t launch_stage_a(Device* d, const PopCols& pc, const GenotypeParams& g, int ploidy, const QueueSite* queue,
                                  const unsigned long long* qn, int64_t qcap, PopStage& st, unsigned long long* ctr,
                                  uint32_t* need_clear, int64_t need_words) {
-    hipLaunchKernelGGL(pc.sta_gcol ? k_stage_a<true> : k_stage_a<false>, dim3(pc.sta_grid), dim3(64),
+    const bool wide = d->n_samples > kPopNarrowSamples;
+    auto kern = wide ? (pc.sta_gcol ? k_stage_a<true, true> : k_stage_a<false, true>)
+                     : (pc.sta_gcol ? k_stage_a<true, false> : k_stage_a<false, false>);
+    hipLaunchKernelGGL(kern, dim3(pc.sta_grid), dim3(64),
                        pc.sta_gcol ? (size_t)0 : (size_t)64 * (size_t)d->pop_stride, d->stream, queue, qn, qcap,
                        pop_gather_of(d, pc.sta_gcol), (const LikTables*)d->d_tables, g, (int32_t)ploidy, st.pmask, st.qB, ctr + 7,
-                       st.cap, ctr, need_clear, need_words);
+                       st.cap, ctr, need_clear, need_words, st.mwords);
     return launch_check();
 }
 // KPM over a queue (mode 1: columns gathered from the population layout; 0: the realigner regions' site-major pile)
@@ -4119,6 +4424,14 @@ static hipError_t launch_kpm(Device* d, const PopCols& pc, int mode, const Genot
                              const QueueSite* queue, const unsigned long long* qn, int64_t qcap, ngsep_popsite_out* sites,
                              ngsep_sample_call* calls, unsigned long long* ctr, int64_t cap, unsigned long long* stamps,
                              hipEvent_t ev_end) {
+    if (d->n_samples > kPopNarrowSamples) {
+        (void)stamps;
+        hipExtLaunchKernelGGL(kpm_wide_kernel(ploidy, mode), dim3(pc.kpm_grid), dim3(kPopThreads), 0, d->stream, nullptr, ev_end, 0,
+                              queue, qn, qcap, (const uint8_t*)d->d_ppile, (const int32_t*)d->d_prow, (const int64_t*)d->d_pboff,
+                              pop_gather_of(d, mode == 1), (const LikTables*)d->d_tables, g, d->n_samples, min_adf, (int32_t)ploidy,
+                              (const PoolTables*)(ploidy >= 3 ? d->d_pool : nullptr), sites, calls, ctr, cap, d->d_wstate);
+        return launch_check();
+    }
     const bool gcol = mode == 1 && pc.kpm_gcol;
     const size_t lds = mode == 1 && !gcol ? (size_t)(d->n_samples + 1) * (size_t)d->pop_stride : 0;
     hipExtLaunchKernelGGL(kpm_kernel(ploidy, mode, gcol), dim3(mode == 1 ? pc.kpm_grid : kpm_grid(d)), dim3(kPopThreads), lds,
@@ -4146,7 +4459,6 @@ int device_run_multi(Device* d, const Staged& s, const LikTables& t, const Genot
     auto t0 = std::chrono::steady_clock::now();
     const int32_t S = d->n_samples;
     if (S <= 0 || n_samples != S) { err = "multisample run without samples (ngsep_set_samples)"; return -1; }
-    if (S > kMaxSamplesDevice) { err = "too many samples for one device run"; return -1; }
     const bool timing = diag_env("NGSEP_TIMING") != nullptr;
     if (timing && !d->d_stamps) HIP_TRY(hipMalloc(&d->d_stamps, 16 * sizeof(unsigned long long)));
     if (timing) HIP_TRY(hipMemsetAsync(d->d_stamps, 0, 16 * sizeof(unsigned long long), d->stream));
@@ -4176,7 +4488,7 @@ int device_run_multi(Device* d, const Staged& s, const LikTables& t, const Genot
     // KLM + KQN, timed together by events bound to their dispatches (ev 0-1), KPM by ev 1-2
     const bool mknown = d->n_mforced >= 0;             // -knownVariants (and the realigner's regions): the queue is given
     const bool two = pop_two_stage(d, g, min_adf, ploidy, mknown);
-    if (two) HIP_TRY(d->pstage.ensure(d->cap_hard, d->g_len / 32 + 1, d->stream));
+    if (two) HIP_TRY(d->pstage.ensure(d->cap_hard, d->g_len / 32 + 1, S, d->stream));
     if (mknown || !d->prg) {
         HIP_TRY(hipEventRecord(d->ev[0], d->stream));
         HIP_TRY(hipEventRecord(d->ev[1], d->stream));
@@ -4408,7 +4720,6 @@ int device_submit_multi(Device* d, const LikTables& t, const GenotypeParams& g, 
     HIP_TRY(hipSetDevice(d->ordinal));
     const int32_t S = d->n_samples;
     if (S <= 0 || n_samples != S) { err = "multisample run without samples (ngsep_set_samples)"; return -1; }
-    if (S > kMaxSamplesDevice) { err = "too many samples for one device run"; return -1; }
     if (ploidy >= 3 && !d->pool_valid) { err = "ploidy >= 3 without pool tables (device_set_pool)"; return -1; }
     if (d->minflight >= 2) { err = "two staged runs already in flight: collect first"; return -1; }
     MultiSlot& m = d->mslot[d->mnext];
@@ -4458,7 +4769,7 @@ int device_submit_multi(Device* d, const LikTables& t, const GenotypeParams& g, 
     const bool mknown = d->n_mforced >= 0;             // -knownVariants: the input variants are the queue
     if (!mknown && !d->prg) { err = "multisample run without a population layout"; return -1; }
     const bool two = pop_two_stage(d, g, min_adf, ploidy, mknown);
-    if (two) HIP_TRY(m.stage.ensure(m.cap_hard, nwords, d->stream));
+    if (two) HIP_TRY(m.stage.ensure(m.cap_hard, nwords, S, d->stream));
     if (mknown) {
         HIP_TRY(hipEventRecord(m.ev[0], d->stream));
         HIP_TRY(hipEventRecord(m.ev[1], d->stream));
