@@ -379,6 +379,30 @@ int ngsep_clear_coverage(ngsep_ctx* ctx);
 /* path B: `CoverageStats -i BAM -o OUT [-minMQ N]` (CoverageStatisticsCalculator.processFile, :99-122) */
 int ngsep_coverage_bam(ngsep_ctx* ctx, const char* bam_path, const char* out_path);
 
+/* ---- BasePairQualityStatisticsCalculator (alignments/BasePairQualityStatisticsCalculator.java:146-258; command
+ * BasePairQualStats) ----  New entry points of ABI 12 (no structure changes).  For every mapped alignment the reader
+ * returns (filter: FLAG_READ_UNMAPPED alone, :179-180) the device compares each read base that is one of ACGT and
+ * aligned by an M / = / X item with the reference base there (one of ACGT, case folded), and counts the mismatches per
+ * read position from the 5' end, the alignments per read length and the totals, each also for the unique alignments
+ * (no 0x1000 FLAG_MULTIPLE_ALN in flags; -minMQ is params.min_mq).  A reference must be loaded (NGSEP_E_INVALID
+ * otherwise); there is no CPU path (NGSEP_E_DEVICE without a HIP device).  Counts accumulate over calls until
+ * ngsep_clear_qualstats (the reference's init(), :162-171).  Records without read characters (SEQ '*', seq_len 0) are
+ * skipped: the reference fails on them.
+ * path B: run()'s loop over the files (:149-152), each read to its end in file order; printStatistics' text to
+ * out_path ("-" = stdout, NULL = no text).  NGSEP_E_IO names a file that cannot be opened. */
+int ngsep_qualstats_bams(ngsep_ctx* ctx, const char* const* bam_paths, int32_t n_files, const char* out_path);
+/* path A: reader-filtered alignments pushed by the host (processFile's loop body, :184-229); the characters are packed
+ * to 4 bits on the host threads, the rest is the same device path */
+int ngsep_qualstats_alignments(ngsep_ctx* ctx, const ngsep_read_batch* batch);
+/* the counts so far: *n_out = the longest read seen; for i < min(*n_out, cap): mismatches[i] and mismatches_unique[i]
+ * at read position i + 1, alns_by_length[i] and unique_by_length[i] = alignments of read length i + 1 (the report's
+ * columns 4 and 5 are their sums from i on); totals[4] = alignments, unique alignments, bases, unique bases
+ * (getTotalAlignments, getReadsUniqueMapping, getTotalBases, getBasesUniqueMapping).  Any pointer may be NULL. */
+int ngsep_fetch_qualstats(ngsep_ctx* ctx, int64_t* mismatches, int64_t* mismatches_unique, int64_t* alns_by_length,
+                          int64_t* unique_by_length, int64_t cap, int64_t* n_out, int64_t* totals);
+int ngsep_write_qualstats(ngsep_ctx* ctx, const char* path);   /* printStatistics (:248-258); "-" = stdout */
+int ngsep_clear_qualstats(ngsep_ctx* ctx);
+
 /* ---- BAM reading (ReadAlignmentFileReader semantics, alignments/io/ReadAlignmentFileReader.java:219-354) ---- */
 typedef struct ngsep_bam ngsep_bam;
 int  ngsep_bam_open(ngsep_ctx* ctx, const char* path, ngsep_bam** out);

@@ -230,6 +230,12 @@ SIGNATURES = {
     "ngsep_fetch_rac": (ctypes.c_int, [_CTX, P(ctypes.c_double), P(ctypes.c_double), P(ctypes.c_double)]),
     "ngsep_write_rac": (ctypes.c_int, [_CTX, ctypes.c_char_p]),
     "ngsep_clear_rac": (ctypes.c_int, [_CTX]),
+    "ngsep_qualstats_bams": (ctypes.c_int, [_CTX, P(ctypes.c_char_p), ctypes.c_int32, ctypes.c_char_p]),
+    "ngsep_qualstats_alignments": (ctypes.c_int, [_CTX, P(NgsepReadBatch)]),
+    "ngsep_fetch_qualstats": (ctypes.c_int, [_CTX, P(ctypes.c_int64), P(ctypes.c_int64), P(ctypes.c_int64), P(ctypes.c_int64),
+                                             ctypes.c_int64, P(ctypes.c_int64), P(ctypes.c_int64)]),
+    "ngsep_write_qualstats": (ctypes.c_int, [_CTX, ctypes.c_char_p]),
+    "ngsep_clear_qualstats": (ctypes.c_int, [_CTX]),
 }
 
 _lib = None

@@ -1273,6 +1273,48 @@ extern "C" int ngsep_rac_bam(ngsep_ctx* c, const char* bam_path, const char* out
     return ngsep_write_rac(c, out_path);
 }
 
+// BasePairQualityStatisticsCalculator.processFile's reader (alignments/BasePairQualityStatisticsCalculator.java:178-181):
+// filterFlags = FLAG_READ_UNMAPPED alone -- secondary, supplementary, duplicate, QC-fail and multiple alignments are
+// all read (the repeated-record and malformed-record skips are the reader's own, whatever the filter)
+static void filter_unmapped_only(ngsep_bam* b) { b->filter_flags = 0x4; }
+
+// BasePairQualityStatisticsCalculator.run (:146-160) over BAM files: every file through KBQ (qualstats.hip) batch by
+// batch, the counts accumulating on the device; printStatistics' text to out_path
+extern "C" int ngsep_qualstats_bams(ngsep_ctx* c, const char* const* bam_paths, int32_t n_files, const char* out_path) {
+    if (!c || !bam_paths || n_files < 1) return NGSEP_E_INVALID;
+    for (int32_t k = 0; k < n_files; k++)
+        if (!bam_paths[k]) return NGSEP_E_INVALID;
+    if (c->seq_names.empty()) return ngsep::qualstats_device(c);        // (NGSEP_E_INVALID: the genome is required, :147)
+    const auto t0 = std::chrono::steady_clock::now();
+    // the device comes up and takes the genome's codes on a thread of its own while the first file is opened and its
+    // first blocks inflate (as call_bam's start_device_init); a failure there is reported before any file's
+    int rc_dev = NGSEP_OK;
+    std::string err_dev;
+    std::thread dev([&] { rc_dev = ngsep::qualstats_device_start(c, err_dev); });
+    int rc = NGSEP_OK;
+    for (int32_t k = 0; k < n_files && rc == NGSEP_OK; k++) {
+        ngsep_bam* b = nullptr;
+        rc = ngsep_bam_open(c, bam_paths[k], &b);
+        if (dev.joinable()) {
+            dev.join();
+            if (rc_dev != NGSEP_OK) {
+                if (b) ngsep_bam_close(b);
+                return set_error(c, rc_dev, err_dev);
+            }
+        }
+        if (rc != NGSEP_OK) break;
+        filter_unmapped_only(b);
+        rc = for_each_batch(c, b, [&](const ngsep::PackedBatch& batch) { return ngsep::qualstats_batch(c, &batch.b, true); });
+        ngsep_bam_close(b);
+    }
+    if (env_hook("NGSEP_HOST_TIMING"))
+        std::fprintf(stderr, "[ngsep host] qualstats: files %.3f s in all; device and genome codes %.3f s (beside the first open), batch staging %.3f s, "
+                     "upload + KBQ %.3f s (KBQ on the device %.3f ms)\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
+                     c->qs_t_setup, c->qs_t_pack, c->qs_t_run, c->stats.scan_ms);
+    if (rc != NGSEP_OK) return rc;
+    return out_path ? ngsep_write_qualstats(c, out_path) : NGSEP_OK;
+}
+
 extern "C" int ngsep_call_bam(ngsep_ctx* c, const char* bam_path, const char* out_vcf_path) {
     if (!c || !bam_path || !out_vcf_path) return NGSEP_E_INVALID;
     return ngsep::call_bam(c, bam_path, out_vcf_path);

@@ -217,6 +217,40 @@ static int main_rac(int argc, char** argv, int i) {
     return 0;
 }
 
+// `ngsep-amd BasePairQualStats -r REF [-o OUT] [-minMQ N] BAM...`
+// (BasePairQualityStatisticsCalculator.main/run, alignments/BasePairQualityStatisticsCalculator.java:137-160):
+// writes to standard output unless -o is given
+static int main_qualstats(int argc, char** argv, int i) {
+    ngsep_params p;
+    ngsep_params_default(&p);
+    const char *ref = nullptr, *outp = "-";
+    int device = 0;
+    std::vector<const char*> bams;
+    for (; i < argc; i++) {
+        const char* a = argv[i];
+        const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
+        auto takes = [&](const char* name) { if (std::strcmp(a, name) == 0 && v) { i++; return true; } return false; };
+        if (takes("-r")) ref = v;
+        else if (takes("-o")) outp = v;
+        else if (takes("-minMQ")) p.min_mq = std::atoi(v);
+        else if (takes("-device")) device = std::atoi(v);
+        else if (a[0] == '-') { std::fprintf(stderr, "unknown or unsupported option %s\n", a); return 2; }
+        else bams.push_back(a);
+    }
+    if (!ref || bams.empty()) {
+        std::fprintf(stderr, "The file with the reference genome is a required parameter\n"
+                             "usage: ngsep-amd BasePairQualStats -r <reference.fa> [-o <out.txt>] [-minMQ N] [-device N] <BAM>...\n");
+        return 2;
+    }
+    ngsep_ctx* c = nullptr;
+    int rc = ngsep_open(device, &p, &c);
+    if (rc == NGSEP_OK) rc = ngsep_load_fasta(c, ref);
+    if (rc == NGSEP_OK) rc = ngsep_qualstats_bams(c, bams.data(), (int32_t)bams.size(), outp);
+    if (rc != NGSEP_OK) { std::fprintf(stderr, "error %d: %s\n", rc, c ? ngsep_last_error(c) : "open failed"); if (c) ngsep_close(c); return 1; }
+    ngsep_close(c);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     ngsep_params p;
     ngsep_params_default(&p);
@@ -228,6 +262,7 @@ int main(int argc, char** argv) {
     if (i < argc && std::strcmp(argv[i], "MultisampleVariantsDetector") == 0) return main_mvd(argc, argv, i + 1);
     if (i < argc && std::strcmp(argv[i], "CoverageStats") == 0) return main_coverage(argc, argv, i + 1);
     if (i < argc && std::strcmp(argv[i], "RelativeAlleleCounts") == 0) return main_rac(argc, argv, i + 1);
+    if (i < argc && std::strcmp(argv[i], "BasePairQualStats") == 0) return main_qualstats(argc, argv, i + 1);
     if (i < argc && std::strcmp(argv[i], "SingleSampleVariantsDetector") == 0) i++;
     else if (i < argc && argv[i][0] != '-') { std::fprintf(stderr, "unsupported command %s\n", argv[i]); return usage(argv[0]); }
     for (; i < argc; i++) {

@@ -3344,6 +3344,7 @@ extern "C" int ngsep_close(ngsep_ctx* c) {
     c->arena.release();
     if (c->dev) device_destroy(c->dev);
     if (c->cov_dev) cov_destroy(c->cov_dev);
+    if (c->qs_dev) qs_destroy(c->qs_dev);
     for (auto& m : c->gz_in_pool) ngsep::gz_host_free(m.first);
     for (auto& m : c->gz_chunk_pool) ngsep::gz_host_free(m.first);
     if (c->gz) ngsep::gz_destroy(c->gz);
@@ -3455,6 +3456,187 @@ extern "C" int ngsep_write_coverage(ngsep_ctx* c, const char* path) {
         out += line;
     }
     std::snprintf(line, sizeof line, "More\t%lld\t%lld\n", (long long)hi, (long long)hu);
+    out += line;
+    const bool to_stdout = std::strcmp(path, "-") == 0;
+    FILE* f = to_stdout ? stdout : std::fopen(path, "w");
+    if (!f) return set_error(c, NGSEP_E_IO, std::string("cannot write ") + path);
+    const bool ok = std::fwrite(out.data(), 1, out.size(), f) == out.size();
+    if (to_stdout) std::fflush(f); else std::fclose(f);
+    return ok ? NGSEP_OK : set_error(c, NGSEP_E_IO, std::string("cannot write ") + path);
+}
+
+// ---- BasePairQualityStatisticsCalculator (alignments/BasePairQualityStatisticsCalculator.java:146-258) ----
+namespace ngsep {
+// the device and the genome's codes on it: run() requires the genome (:147), and there is no CPU fallback
+// (err instead of the context's message: path B runs this on a thread of its own while the first file is opened)
+int qualstats_device_start(ngsep_ctx* c, std::string& err) {
+    if (c->seq_names.empty()) { err = "The file with the reference genome is a required parameter"; return NGSEP_E_INVALID; }
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!c->qs_dev) {
+        c->qs_dev = qs_create(c->device, err);
+        if (!c->qs_dev) return NGSEP_E_DEVICE;
+    }
+    if (c->qs_ref_seqs != c->seq_bases.size()) {
+        if (qs_set_reference(c->qs_dev, c->seq_bases, err) != 0) return NGSEP_E_DEVICE;
+        c->qs_seq_start.assign(c->seq_bases.size() + 1, 0);
+        for (size_t k = 0; k < c->seq_bases.size(); k++) c->qs_seq_start[k + 1] = c->qs_seq_start[k] + (int64_t)c->seq_bases[k].size();
+        c->qs_ref_seqs = c->seq_bases.size();
+    }
+    c->qs_t_setup += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return NGSEP_OK;
+}
+int qualstats_device(ngsep_ctx* c) {
+    std::string err;
+    const int rc = qualstats_device_start(c, err);
+    return rc == NGSEP_OK ? rc : set_error(c, rc, err);
+}
+
+// processFile's loop (:183-235) over one batch: the records go to the device as they are (BAM batches: the 4-bit SEQ
+// bytes copied, else the characters packed two per byte; the CIGAR words copied), one header each; no per-base work here
+int qualstats_batch(ngsep_ctx* c, const ngsep_read_batch* b, bool packed) {
+    int rc = qualstats_device(c);
+    if (rc != NGSEP_OK) return rc;
+    const int64_t n = b->n_reads;
+    if (n < 0) return set_error(c, NGSEP_E_INVALID, "negative number of alignments");
+    if (n == 0) return NGSEP_OK;
+    if (!b->seq_id || !b->first || !b->flags || !b->cigar_off || !b->cigar_n || !b->cigar || !b->seq_off || !b->seq_len || !b->bases)
+        return set_error(c, NGSEP_E_INVALID, "alignment batch with a null array");
+    // the records KBQ takes: mapped (the reader's only filter, :179-180) and with read characters (SEQ '*': the
+    // reference fails on getReadCharacters() == null at :191), their offsets validated
+    const int32_t n_seq = (int32_t)c->seq_bases.size();
+    std::vector<int64_t> keep;
+    keep.reserve((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        if (b->flags[i] & 0x4) continue;
+        const int32_t l = b->seq_len[i];
+        if (l == 0) continue;
+        if (l < 0 || b->cigar_n[i] < 0 || b->cigar_off[i] < 0 || b->seq_off[i] < 0 || b->seq_id[i] < 0 || b->seq_id[i] >= n_seq)
+            return set_error(c, NGSEP_E_INVALID, "alignment " + std::to_string(i) + " of the batch has an invalid sequence, length or offset");
+        if (b->cigar_n[i] >= kQsMaxCigar) return set_error(c, NGSEP_E_UNSUPPORTED, "alignment with 2^28 or more CIGAR items");
+        keep.push_back(i);
+    }
+    static const uint8_t* nib = [] {                 // character -> BAM nibble ("=ACMGRSVTWYHKDBN"; anything else N)
+        static uint8_t t[256];
+        static const char kNt[] = "=ACMGRSVTWYHKDBN";
+        for (int v = 0; v < 256; v++) t[v] = 15;
+        for (int k = 0; k < 16; k++) { t[(uint8_t)kNt[k]] = (uint8_t)k; t[(uint8_t)std::tolower((unsigned char)kNt[k])] = (uint8_t)k; }
+        return t;
+    }();
+    std::vector<uint32_t> co, so;
+    std::string err;
+    for (size_t k0 = 0; k0 < keep.size();) {
+        // one launch: records up to the launch limits (engine.hpp kQsMax*)
+        co.clear();
+        so.clear();
+        int64_t nc = 0, ns = 0, maxl = 0;
+        size_t k1 = k0;
+        while (k1 < keep.size() && (int64_t)(k1 - k0) < kQsMaxRecords) {
+            const int64_t i = keep[k1];
+            const int64_t wc = b->cigar_n[i], sb = ((int64_t)b->seq_len[i] + 1) / 2;
+            if (k1 > k0 && (nc + wc > kQsMaxCigar || ns + sb > kQsMaxSeqBytes)) break;
+            co.push_back((uint32_t)nc);
+            so.push_back((uint32_t)ns);
+            nc += wc;
+            ns += sb;
+            maxl = std::max<int64_t>(maxl, b->seq_len[i]);
+            k1++;
+        }
+        const int64_t m = (int64_t)(k1 - k0);
+        const auto t0 = std::chrono::steady_clock::now();
+        QsRec* hrec = nullptr;
+        uint32_t* hcig = nullptr;
+        uint8_t* hseq = nullptr;
+        if (qs_stage(c->qs_dev, m, nc, ns, &hrec, &hcig, &hseq, err) != 0) return set_error(c, NGSEP_E_DEVICE, err);
+        parallel_for(m, 1024, [&](int64_t lo, int64_t hi) {
+            for (int64_t k = lo; k < hi; k++) {
+                const int64_t i = keep[k0 + (size_t)k];
+                const int32_t l = b->seq_len[i], sid = b->seq_id[i];
+                QsRec& h = hrec[k];
+                h.gfirst = c->qs_seq_start[(size_t)sid] + (int64_t)b->first[i] - 1;
+                h.seq_off = so[(size_t)k];
+                h.cig_off = co[(size_t)k];
+                h.first = b->first[i];
+                h.seq_len = (int32_t)std::min<int64_t>((int64_t)c->seq_bases[(size_t)sid].size(), INT32_MAX);
+                h.l_seq = l;
+                // isUnique: no FLAG_MULTIPLE_ALN (ReadAlignment.java:488); isNegativeStrand: 0x10
+                h.ncf = ((uint32_t)b->cigar_n[i] << 2) | ((b->flags[i] & 0x1000) ? 0u : 2u) | ((b->flags[i] & 0x10) ? 1u : 0u);
+                std::memcpy(hcig + co[(size_t)k], b->cigar + b->cigar_off[i], sizeof(int32_t) * (size_t)b->cigar_n[i]);
+                uint8_t* dst = hseq + so[(size_t)k];
+                const uint8_t* src = reinterpret_cast<const uint8_t*>(b->bases) + b->seq_off[i];
+                if (packed) {
+                    std::memcpy(dst, src, ((size_t)l + 1) / 2);
+                } else {
+                    for (int32_t j = 0; j + 1 < l; j += 2) dst[j >> 1] = (uint8_t)((nib[src[j]] << 4) | nib[src[j + 1]]);
+                    if (l & 1) dst[l >> 1] = (uint8_t)(nib[src[l - 1]] << 4);
+                }
+            }
+        });
+        const auto t1 = std::chrono::steady_clock::now();
+        if (qs_run(c->qs_dev, m, nc, ns, maxl, err) != 0) return set_error(c, NGSEP_E_DEVICE, err);
+        c->qs_t_pack += std::chrono::duration<double>(t1 - t0).count();
+        c->qs_t_run += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+        c->qs_npos = std::max(c->qs_npos, maxl);
+        c->stats.scan_ms = qs_kernel_ms(c->qs_dev);
+        k0 = k1;
+    }
+    return NGSEP_OK;
+}
+}  // namespace ngsep
+
+extern "C" int ngsep_qualstats_alignments(ngsep_ctx* c, const ngsep_read_batch* b) {
+    if (!c || !b) return NGSEP_E_INVALID;
+    return qualstats_batch(c, b, false);
+}
+
+extern "C" int ngsep_fetch_qualstats(ngsep_ctx* c, int64_t* mismatches, int64_t* mismatches_unique, int64_t* alns_by_length,
+                                     int64_t* unique_by_length, int64_t cap, int64_t* n_out, int64_t* totals) {
+    if (!c || cap < 0) return NGSEP_E_INVALID;
+    const int64_t n = c->qs_npos;
+    if (n_out) *n_out = n;
+    std::vector<uint64_t> v((size_t)(4 * n + 4), 0);
+    if (c->qs_dev) {
+        std::string err;
+        if (qs_fetch(c->qs_dev, n, v.data(), err) != 0) return set_error(c, NGSEP_E_DEVICE, err);
+    }
+    int64_t* dst[4] = {mismatches, mismatches_unique, alns_by_length, unique_by_length};
+    for (int a = 0; a < 4; a++)
+        if (dst[a])
+            for (int64_t i = 0; i < std::min(n, cap); i++) dst[a][i] = (int64_t)v[(size_t)a * (size_t)n + (size_t)i];
+    if (totals)
+        for (int k = 0; k < 4; k++) totals[k] = (int64_t)v[(size_t)(4 * n + k)];
+    return NGSEP_OK;
+}
+
+extern "C" int ngsep_clear_qualstats(ngsep_ctx* c) {
+    if (!c) return NGSEP_E_INVALID;
+    c->qs_npos = 0;
+    if (c->qs_dev) {
+        std::string err;
+        if (qs_clear(c->qs_dev, err) != 0) return set_error(c, NGSEP_E_DEVICE, err);
+    }
+    return NGSEP_OK;
+}
+
+// printStatistics (:248-258): per read position the mismatches and the alignments at least that long (makeCumulative,
+// :322-332), an empty line, the totals
+extern "C" int ngsep_write_qualstats(ngsep_ctx* c, const char* path) {
+    if (!c || !path) return NGSEP_E_INVALID;
+    int64_t n = 0, tot[4] = {0, 0, 0, 0};
+    int rc = ngsep_fetch_qualstats(c, nullptr, nullptr, nullptr, nullptr, 0, &n, nullptr);
+    if (rc != NGSEP_OK) return rc;
+    std::vector<int64_t> m((size_t)n), mu((size_t)n), a((size_t)n), au((size_t)n);
+    rc = ngsep_fetch_qualstats(c, m.data(), mu.data(), a.data(), au.data(), n, &n, tot);
+    if (rc != NGSEP_OK) return rc;
+    for (int64_t i = n - 2; i >= 0; i--) { a[(size_t)i] += a[(size_t)i + 1]; au[(size_t)i] += au[(size_t)i + 1]; }
+    std::string out;
+    char line[160];
+    for (int64_t i = 0; i < n; i++) {
+        std::snprintf(line, sizeof line, "%lld\t%lld\t%lld\t%lld\t%lld\n", (long long)i + 1, (long long)m[(size_t)i],
+                      (long long)mu[(size_t)i], (long long)a[(size_t)i], (long long)au[(size_t)i]);
+        out += line;
+    }
+    std::snprintf(line, sizeof line, "\nAlignments\t%lld\t%lld\nBases\t%lld\t%lld\n", (long long)tot[0], (long long)tot[1],
+                  (long long)tot[2], (long long)tot[3]);
     out += line;
     const bool to_stdout = std::strcmp(path, "-") == 0;
     FILE* f = to_stdout ? stdout : std::fopen(path, "w");

@@ -401,6 +401,23 @@ void parallel_for(int64_t n, int64_t grain, F&& fn) {
 struct Device;   // kernels.hip
 struct CovDevice;   // coverage.hip
 struct GzDevice;    // inflate.hip
+struct QsDevice;    // qualstats.hip
+
+// KBQ's header of one record (qualstats.hip): where its SEQ bytes and CIGAR words lie in the batch buffers, where its
+// first aligned position lies in the genome's code array and in its own sequence
+struct QsRec {
+    int64_t gfirst;        // index of 1-based position `first` in the device's genome codes (sequences back to back)
+    uint32_t seq_off;      // byte offset of the 4-bit SEQ in the batch's SEQ buffer
+    uint32_t cig_off;      // word offset of the CIGAR in the batch's CIGAR buffer
+    int32_t first;         // 1-based first aligned position
+    int32_t seq_len;       // the sequence's length: a position outside [1, seq_len] does not count
+    int32_t l_seq;
+    uint32_t ncf;          // n_cigar << 2 | unique << 1 | negative strand
+};
+static_assert(sizeof(QsRec) == 32, "QsRec layout");
+constexpr int64_t kQsMaxRecords = (int64_t)1 << 20;    // records of one KBQ launch (a workgroup's 32-bit LDS counts cannot carry)
+constexpr int64_t kQsMaxSeqBytes = (int64_t)1 << 30;   // ... their SEQ bytes and CIGAR words (32-bit offsets): a launch takes
+constexpr int64_t kQsMaxCigar = (int64_t)1 << 28;      // records up to these sums, or one record alone
 
 // Pinned host memory (kernels.hip).  Every host address a device copy reads or writes lies in a block recorded in
 // one registry: pinned_alloc's blocks (a page-aligned block registered with hipHostRegister, or hipHostMalloc when
@@ -814,6 +831,12 @@ struct ngsep_ctx {
     ngsep::CovDevice* cov_dev = nullptr;
     bool cov_staged = false;
     std::vector<uint64_t> cov_hist;          // 2 x (max_coverage + 1), accumulated over runs
+    // BasePairQualityStatisticsCalculator (ngsep_qualstats_*): the counts live on the device until fetched
+    ngsep::QsDevice* qs_dev = nullptr;
+    size_t qs_ref_seqs = 0;                  // sequences whose codes the device holds
+    std::vector<int64_t> qs_seq_start;       // their starts in the device's genome codes
+    int64_t qs_npos = 0;                     // the longest read seen (the report's rows)
+    double qs_t_setup = 0, qs_t_pack = 0, qs_t_run = 0;   // NGSEP_HOST_TIMING: device + genome codes, batch staging, upload + KBQ (s)
     // multisample (ngsep_set_samples)
     std::vector<std::string> sample_ids;
     std::vector<int32_t> rg_sample, rg_rank;
@@ -902,6 +925,20 @@ void cov_destroy(CovDevice* d);
 int cov_upload(CovDevice* d, const std::vector<int64_t>& gfirst, const std::vector<uint32_t>& spanu, int64_t g_len,
                int32_t max_span, std::string& err);
 int cov_run(CovDevice* d, int32_t max_cov, uint64_t* hist_out, double* kernel_ms, std::string& err);
+// qualstats.hip
+QsDevice* qs_create(int ordinal, std::string& err);
+void qs_destroy(QsDevice* d);
+int qs_set_reference(QsDevice* d, const std::vector<std::string>& seqs, std::string& err);
+int qs_stage(QsDevice* d, int64_t n_rec, int64_t n_cig, int64_t n_seq, QsRec** rec, uint32_t** cig, uint8_t** seq, std::string& err);
+int qs_run(QsDevice* d, int64_t n_rec, int64_t n_cig, int64_t n_seq, int64_t max_lseq, std::string& err);
+int qs_fetch(QsDevice* d, int64_t n, uint64_t* out, std::string& err);
+int qs_clear(QsDevice* d, std::string& err);
+double qs_kernel_ms(const QsDevice* d);
+// engine.cpp: one batch of reader-filtered alignments through KBQ (packed: BAM encoding, bam.cpp's batches)
+int qualstats_batch(ngsep_ctx* c, const ngsep_read_batch* b, bool packed);
+// ... and what it needs first: a loaded reference (NGSEP_E_INVALID), the device (NGSEP_E_DEVICE), the genome's codes on it
+int qualstats_device(ngsep_ctx* c);
+int qualstats_device_start(ngsep_ctx* c, std::string& err);   // the same with the message in err (any thread)
 // inflate.hip: BGZF blocks inflated on the device (bam.cpp's decoder; two slots in flight)
 struct GzDevice;
 GzDevice* gz_create(int ordinal, std::string& err);

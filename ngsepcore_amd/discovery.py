@@ -6,6 +6,7 @@ Names, option meanings and defaults follow the reference:
   * AlignmentsPileupGenerator.processAlignments / notifyEndOfAlignments
     (discovery/AlignmentsPileupGenerator.java:334-361,447-452) -> GpuPileupSession
   * SingleSampleVariantPileupListener.getCalledVariants (:139-141) -> GpuPileupSession.getCalledVariants
+  * BasePairQualityStatisticsCalculator (src/ngsep/alignments/BasePairQualityStatisticsCalculator.java:44-334)
 Errors surface as NgsepError (the reference throws IOException / IllegalArgumentException).
 """
 from __future__ import annotations
@@ -667,3 +668,157 @@ class RelativeAlleleCountsCalculator:
             self._collect(s)
             if out_path:
                 s._check(s._lib.ngsep_write_rac(s._ctx, out_path.encode()))
+
+
+class BasePairQualityStatisticsCalculator:
+    """Drop-in for ngsep.alignments.BasePairQualityStatisticsCalculator (alignments/BasePairQualityStatisticsCalculator.java:
+    44-334; command BasePairQualStats): mismatches per read position from the 5' end, for all alignments and for the
+    unique ones, the per-base loop on the GPU (qualstats.hip, KBQ).  The counts live in one device context from the
+    first processFile until close(); run() starts from zero (init(), :162-171)."""
+
+    DEF_MIN_MQ_UNIQUE_ALIGNMENT = 20
+
+    def __init__(self):
+        self.params = default_params()
+        self.params.process_secondary = 1      # the reader's filter is FLAG_READ_UNMAPPED alone (:179-180)
+        self.inputFiles: List[str] = []
+        self.outputFile: Optional[str] = None
+        self.genomeFile: Optional[str] = None
+        self.contigs = None                    # (name, bases) pairs instead of a FASTA file
+        self.device = 0
+        self._s: Optional[GpuPileupSession] = None
+        self.mismatches: List[int] = []
+        self.mismatchesReadsUniqueMapping: List[int] = []
+        self.alnsByLength: List[int] = []
+        self.readsUniqueMappingByLength: List[int] = []
+        self.totalAlignments = self.totalBases = self.readsUniqueMapping = self.basesUniqueMapping = 0
+
+    def setInputFiles(self, v: Sequence[str]): self.inputFiles = list(v)
+    def getInputFiles(self) -> List[str]: return self.inputFiles
+    def setOutputFile(self, v: Optional[str]): self.outputFile = v
+    def getOutputFile(self) -> Optional[str]: return self.outputFile
+    def setGenome(self, v: str): self.genomeFile = v
+    def setMinMQ(self, v: int): self.params.min_mq = int(v)
+    def getMinMQ(self) -> int: return self.params.min_mq
+    def getTotalAlignments(self) -> int: return self.totalAlignments
+    def getTotalBases(self) -> int: return self.totalBases
+    def getReadsUniqueMapping(self) -> int: return self.readsUniqueMapping
+    def getBasesUniqueMapping(self) -> int: return self.basesUniqueMapping
+
+    def _session(self) -> GpuPileupSession:
+        if self._s is None:
+            if self.genomeFile is None and self.contigs is None:
+                raise NgsepError(_lib.NGSEP_E_IO, "The file with the reference genome is a required parameter")
+            s = GpuPileupSession(self.params, self.device)
+            try:
+                if self.genomeFile is not None:
+                    s.load_fasta(self.genomeFile)
+                for name, seq in self.contigs or ():
+                    s.set_reference(name, seq)
+            except Exception:
+                s.close()
+                raise
+            self._s = s
+        return self._s
+
+    def close(self):
+        if self._s is not None:
+            self._s.close()
+            self._s = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _collect(self):
+        s = self._session()
+        n = ctypes.c_int64()
+        s._check(s._lib.ngsep_fetch_qualstats(s._ctx, None, None, None, None, 0, ctypes.byref(n), None))
+        k = max(n.value, 1)
+        arrs = [(ctypes.c_int64 * k)() for _ in range(4)]
+        tot = (ctypes.c_int64 * 4)()
+        s._check(s._lib.ngsep_fetch_qualstats(s._ctx, arrs[0], arrs[1], arrs[2], arrs[3], n.value, ctypes.byref(n), tot))
+        (self.mismatches, self.mismatchesReadsUniqueMapping, self.alnsByLength,
+         self.readsUniqueMappingByLength) = (list(a)[:n.value] for a in arrs)
+        self.totalAlignments, self.readsUniqueMapping, self.totalBases, self.basesUniqueMapping = list(tot)
+
+    def init(self):
+        """init() (:162-171): the counters back to zero."""
+        if self._s is not None:
+            self._s._check(self._s._lib.ngsep_clear_qualstats(self._s._ctx))
+            self._collect()
+
+    def run(self):
+        """run() (:146-160): init, every input file, printStatistics to the output file (stdout when None)."""
+        s = self._session()
+        self.init()
+        if not self.inputFiles:
+            self._collect()
+        else:
+            arr = (ctypes.c_char_p * len(self.inputFiles))(*[f.encode() for f in self.inputFiles])
+            s._check(s._lib.ngsep_qualstats_bams(s._ctx, arr, len(self.inputFiles), None))
+            self._collect()
+        s._check(s._lib.ngsep_write_qualstats(s._ctx, (self.outputFile or "-").encode()))
+
+    def processFile(self, filename: str):
+        """processFile (:177-237): one more file into the counts."""
+        s = self._session()
+        arr = (ctypes.c_char_p * 1)(filename.encode())
+        s._check(s._lib.ngsep_qualstats_bams(s._ctx, arr, 1, None))
+        self._collect()
+
+    def processFileBatches(self, filename: str, batch_reads: int = 1 << 20):
+        """Path A fed by the C++ reader: the file's reader-filtered alignments in batches of batch_reads through
+        ngsep_qualstats_alignments (what a host with its own reader does)."""
+        s = self._session()
+        b = ctypes.c_void_p()
+        s._check(s._lib.ngsep_bam_open(s._ctx, filename.encode(), ctypes.byref(b)))
+        try:
+            batch = NgsepReadBatch()
+            while True:
+                s._check(s._lib.ngsep_bam_next_batch(b, batch_reads, ctypes.byref(batch)))
+                if batch.n_reads == 0:
+                    break
+                s._check(s._lib.ngsep_qualstats_alignments(s._ctx, ctypes.byref(batch)))
+        finally:
+            s._lib.ngsep_bam_close(b)
+        self._collect()
+
+    def processBatches(self, batches):
+        """Path A: reader-filtered alignment batches (flags carry 0x1000 for multiple alignments)."""
+        s = self._session()
+        for b in batches:
+            s._check(s._lib.ngsep_qualstats_alignments(s._ctx, ctypes.byref(b)))
+        self._collect()
+
+    @staticmethod
+    def _cumulative(data: Sequence[int]) -> List[int]:
+        out, t = [0] * len(data), 0
+        for i in range(len(data) - 1, -1, -1):
+            t += data[i]
+            out[i] = t
+        return out
+
+    def printStatistics(self, out=None) -> str:
+        """printStatistics (:248-258)."""
+        ca, cu = self._cumulative(self.alnsByLength), self._cumulative(self.readsUniqueMappingByLength)
+        lines = [f"{i + 1}\t{self.mismatches[i]}\t{self.mismatchesReadsUniqueMapping[i]}\t{ca[i]}\t{cu[i]}"
+                 for i in range(len(self.mismatches))]
+        txt = "\n".join(lines + ["", f"Alignments\t{self.totalAlignments}\t{self.readsUniqueMapping}",
+                                 f"Bases\t{self.totalBases}\t{self.basesUniqueMapping}"]) + "\n"
+        if out is not None:
+            out.write(txt)
+        return txt
+
+    def calculatePercentages(self, uniqueAlignments: bool) -> List[float]:
+        """calculatePercentages (:266-278): 100 x mismatches / alignments at least that long, as Java's double
+        division gives it (0 / 0 = NaN, x / 0 = Infinity)."""
+        m = self.mismatchesReadsUniqueMapping if uniqueAlignments else self.mismatches
+        cum = self._cumulative(self.readsUniqueMappingByLength if uniqueAlignments else self.alnsByLength)
+        out = []
+        for a, b in zip(m, cum):
+            x = 100.0 * a
+            out.append(x / b if b else (float("nan") if x == 0 else float("inf")))
+        return out
