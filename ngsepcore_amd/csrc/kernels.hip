@@ -7,13 +7,15 @@
 //        column space.  This is AlignmentsPileupGenerator.processCurrentPosition
 //        (discovery/AlignmentsPileupGenerator.java:475-498) reduced to the fact that decides whether SNVQ can call a
 //        variant there ("why pruning is exact").
-//   KG  k_gather_kl / k_gather_cols : the queued sites' columns (PileupRecord.getAlleleCalls(1) in pending order)
+//   KG  k_gather_cols : the queued sites' columns (PileupRecord.getAlleleCalls(1) in pending order)
 //        gathered from the read-group layout, the queue compacted.
 //   KQ  k_queue_all : every in-window position queued (dump mode, runs without the exact pruning).
 //   KP  k_posterior : exact CountsHelper tally (pending-list order, bit-exact fp64), posterior and
 //        SNVQ call of the queued candidates (discovery/CountsHelper.java:83-95,209-251,410-495,
 //        VariantDiscoverySNVQAlgorithm.java:100-243, SingleSampleVariantPileupListener.java:213-232);
 //        records go to position buckets.
+//   KGP k_gather_call : KG and KP in one kernel for KL's survivors (diploid / haploid calls): the column stays in
+//        LDS, 16 lanes genotype a site.
 //   KO  ko_fused : position order of the records (rank per bucket) and their (sequence, position).
 //   KLM / KQN / KPM k_scan_pop / k_queue_need / k_posterior_multi : MultisampleVariantsDetector.
 //   KR  k_rac : RelativeAlleleCountsCalculator over the tile-blocked byte pile (engine.cpp build_single_layout).
@@ -150,7 +152,7 @@ struct Device {
     RunSlot slot[2];
     int64_t n_submitted = 0, n_collected = 0;
     // an event between KP and KO costs a few microseconds of idle GPU per pass: recorded only when
-    // the posterior kernel's duration is asked for (NGSEP_TIME_POSTERIOR, diagnostics)
+    // the genotyping kernel's duration is asked for (NGSEP_TIME_POSTERIOR, diagnostics; KGP: gather plus call)
     bool time_posterior = env_hook("NGSEP_TIME_POSTERIOR") != nullptr;
     bool time_scan = diag_env("NGSEP_NO_SCAN_TIMING") == nullptr;   // diagnostics: without KT's events
     hipEvent_t ev[4] = {};
@@ -326,7 +328,7 @@ __device__ __forceinline__ int ev_partner(int k) {
 // (ngsep_site_out layout: seq, gpos, ref|n_alleles|alt|third, genotype|strand_bias|gq, qual|is_call|pool, dp,
 // counts[4], strand_counts[4][2]) and its ten log-conditionals L.  A record the 64 B cannot hold (whole =
 // multi-allelic / pool / dump / full_records, or counts past 65535) goes whole to ext, the SiteRec pointing to it.
-__device__ inline void put_site(SiteRec* __restrict__ slot, ngsep_site_out* __restrict__ ext, unsigned long long* ext_n,
+__device__ __forceinline__ void put_site(SiteRec* __restrict__ slot, ngsep_site_out* __restrict__ ext, unsigned long long* ext_n,
                                 int64_t ext_cap, const uint32_t (&h)[18], const double (&L)[10], bool whole, int ri, int ai) {
     uint32_t big = 0;
 #pragma unroll
@@ -1296,94 +1298,386 @@ __global__ __launch_bounds__(256) void k_gather_cols(const SiteQ* __restrict__ q
     }
 }
 
-// KG for KL's queue (every site's column space reserved: rows <= -3, or -2 when the shard's columns were full):
-// a wave gathers kKgSites sites at once, their chunk loads interleaved (one site's gather is a chain of dependent
-// loads -- block table, headers, units -- so a wave per site leaves the chip waiting).  Compacts like k_gather_cols.
-template <int kKgSites>
-__global__ __launch_bounds__(256) void k_gather_kl(const SiteQ* __restrict__ qin, const unsigned long long* __restrict__ qcnt,
-                                                   int stride, int nshard, int64_t qseg, SiteQ* __restrict__ qout,
-                                                   const int2* __restrict__ rh, const RGroup* __restrict__ grp,
-                                                   const uint64_t* __restrict__ units, const int32_t* __restrict__ blkA,
-                                                   const uint8_t* __restrict__ ref, int64_t n_entries,
-                                                   uint16_t* __restrict__ cols, unsigned long long* __restrict__ counters) {
+// KGP k_gather_call: KG and KP in one kernel for KL's queue (every site's column space reserved: rows <= -3, or -2
+// when the shard's columns were full; diploid or haploid calls, no dump mode).  The wave that gathered four sites
+// genotypes them itself, 16 lanes per site: no column and no compact queue through HBM, one launch, and KP's serial
+// per-site work spread over lanes that sat idle (measurements: DESIGN.md 3 KGP).
+//   * gather: a wave takes kKgpSites sites at once, their chunk loads interleaved (one site's gather is a chain of
+//     dependent loads -- block table, headers, units -- so a wave per site leaves the chip waiting).  A column of up
+//     to kKgpColCap entries (KL's coverage says so beforehand) stays in LDS; a deeper one goes to the space KL
+//     reserved in cols and comes back through the LDS column in windows of kKgpColCap.  The entries gathered are
+//     CountsHelper's total (every one is a nonzero code).
+//   * sums: lane j < 10 of a site's 16 owns L[j] and walks the column in rank order with k_posterior's addend, so
+//     every sum takes the reference's addends in the reference's order (bit-identical).  The integer tallies are LDS
+//     adds from the gathering lanes (as ballots, the 32 wave-uniform counters of four sites spilled the kernel's SGPRs;
+//     counted on the walk they doubled its instructions).
+//   * posterior: lane k owns event k (one pow10_j each); the maximum across the group's lanes, the normaliser by
+//     every lane over the group's 16 events in Java's order (calculatePosteriorProbabilities, CountsHelper.java:
+//     472-495); getIndexesMaxGenotype and the filters as k_posterior; the group's first lane lays the record out.
+// No compact queue is written (counters[2] still gets its length).
+// pow and log10 as calls: inlined, their polynomial constants are hoisted out of the kernel's site loop and held in
+// registers through the gather (26 VGPRs and more; 126 VGPRs against 78 with the calls, DESIGN.md 3 KGP)
+__device__ __attribute__((noinline)) double kgp_pow10(double x) { return pow10_j(x); }
+__device__ __attribute__((noinline)) int kgp_phred(double x) { return phred_d(x); }
+constexpr int kKgpSites = 4;                       // sites per wave: 16 lanes each
+constexpr int kKgpColCap = 128;                    // entries of a site's LDS column (tests/test_gpu_fused_call.py)
+static_assert(kKgpSites * 16 == 64 && kKgpColCap == 16 * 8, "k_gather_call: 16 lanes per site, each stages 8 entries of a window");
+// An LDS column entry, laid out for the walk: bits 0-8 eight times the capped quality (the byte offset into a table;
+// 256 = the tables' zero slot: a call that adds to no sum, q<=3 or not A/C/G/T, CountsHelper.java:214-221), bits 12-13
+// the allele (bits 9-13: eight times the allele, a byte's shift in the lane's table word), bit 14 the negative
+// strand, bit 15 a valid call.  kKgpPad fills a column's last four entries past its rows.
+constexpr uint32_t kKgpPad = 256u;
+__device__ __forceinline__ uint32_t kgp_entry(uint32_t code, uint32_t neg, int max_q) {
+    int qv = (int)(code & 31u);
+    qv = qv > max_q ? max_q : qv;                                       // -maxBaseQS (:217-219)
+    return (code & 0x80u) ? 0x8000u | neg << 14 | ((code >> 5) & 3u) << 12 | (uint32_t)qv << 3 : kKgpPad | neg << 14;
+}
+// v of the lane CTRL names within its row of 16 (DPP)
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v) {
+    const int2 b = __builtin_bit_cast(int2, v);
+    return __builtin_bit_cast(double, make_int2(__builtin_amdgcn_update_dpp(b.x, b.x, CTRL, 0xF, 0xF, false),
+                                                __builtin_amdgcn_update_dpp(b.y, b.y, CTRL, 0xF, 0xF, false)));
+}
+
+// LDS written by some lanes of a wave and read by others of the same wave (LDS operations of a wave are in order)
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ __launch_bounds__(256) void k_gather_call(const SiteQ* __restrict__ qin, const unsigned long long* __restrict__ qcnt,
+                                                     int stride, int nshard, int64_t qseg,
+                                                     const int2* __restrict__ rh, const RGroup* __restrict__ grp,
+                                                     const uint64_t* __restrict__ units, const int32_t* __restrict__ blkA,
+                                                     const uint8_t* __restrict__ ref, int64_t n_entries, uint16_t* cols,
+                                                     unsigned long long* __restrict__ counters,
+                                                     const LikTables* __restrict__ tabs, GenotypeParams gp,
+                                                     SiteRec* __restrict__ brec, int32_t* __restrict__ bcount, int shift,
+                                                     int32_t bcap, ngsep_site_out* __restrict__ ext, unsigned long long* ext_n,
+                                                     int64_t ext_cap) {
+    constexpr int S = kKgpSites;
     __shared__ int64_t s_pre[kKlShards + 1];
+    // A, H, E per capped quality (k_posterior's tables) and a zero, 33 apart: one quality's three are on different
+    // banks.  The columns and the per-lane doubles are padded likewise (the wave's four groups read four addresses)
+    __shared__ double s_t[3 * 33];
+    __shared__ __attribute__((aligned(16))) uint16_t s_col[4][S][kKgpColCap + 8];
+    __shared__ __attribute__((aligned(16))) double s_L[4][72];          // the wave's sums: lane j of site g at 18 g + j
+    __shared__ __attribute__((aligned(16))) double s_ev[4][72];         // the wave's events, likewise
+    __shared__ int32_t s_n[4][kKgpSites];                               // the wave's sites' entries
+    // the wave's sites' counts[a] by strand (a + 4 negative; CountsHelper.java:222-227): LDS adds from the lanes that hold
+    // the calls while the gather waits on memory
+    __shared__ int32_t s_tal[4][kKgpSites][8];
     const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (threadIdx.x < 96)
+        s_t[33 * (threadIdx.x >> 5) + (threadIdx.x & 31)] =
+            (threadIdx.x < 32 ? tabs->A : threadIdx.x < 64 ? tabs->H : tabs->E)[threadIdx.x & 31];
+    else if (threadIdx.x < 99)
+        s_t[33 * (threadIdx.x - 96) + 32] = 0.0;
     kg_segments(qcnt, stride, nshard, qseg, s_pre, counters);
     const int64_t total = s_pre[nshard];
     const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
-    const int64_t w0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    for (int64_t i0 = w0 * kKgSites; i0 < total; i0 += nw * kKgSites) {
-        SiteQ q[kKgSites];
-        int64_t e[kKgSites];
-        int32_t n[kKgSites];
-        uint32_t rcode[kKgSites];
-        bool live[kKgSites];
-#pragma unroll
-        for (int t = 0; t < kKgSites; t++) {
-            const int64_t i = i0 + t;
-            live[t] = false;
-            n[t] = 0;
-            e[t] = 0;
-            rcode[t] = 0;
-            q[t] = SiteQ{0, 0, 0, -2};
-            if (i >= total) continue;
+    const int64_t w0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + wv;
+    const int g = lane >> 4, j = lane & 15;                             // site of the wave, lane of the site
+    // lane j < 10 sums L[j] = L[gi][gj] (upper triangle, ngsep_site_out.logc order)
+    const int gi = (int)((0x3221110000ull >> (4 * j)) & 15ull), gj = (int)((0x3323213210ull >> (4 * j)) & 15ull);
+    // updateCounts (CountsHelper.java:231-248): [i][i] += i==idx ? A : E; [i][j] += (i==idx || j==idx) ? H : E.  The
+    // lane's table per allele of the call, a byte each (in doubles): A (0) or H (33) for its genotype's, E (66) otherwise
+    const uint32_t t_in = gi == gj ? 0u : 33u;
+    const uint32_t lut = (0x42424242u & ~(0xFFu << (8 * gi)) & ~(0xFFu << (8 * gj))) | t_in << (8 * gi) | t_in << (8 * gj);
+    uint16_t* const mycol = s_col[wv][g];
+    double* const Lw = s_L[wv];
+    double* const evw = s_ev[wv];
+    const double* const ge = evw + 18 * g;
+    const double* const gL = Lw + 18 * g;
+    const int slot = 18 * g + j;
+    for (int64_t i0 = w0 * S; i0 < total; i0 += nw * S) {
+        wave_lds_sync();                                                // the wave's LDS is read before its next sites
+        if (lane < 8 * S) (&s_tal[wv][0][0])[lane] = 0;
+        // the lane's site (its 16 lanes load the same entry), then the four sites wave-uniform for the gather
+        SiteQ mq = SiteQ{0, 0, 0, -2};
+        if (i0 + g < total) {
+            const int64_t i = i0 + g;
             int k = 0;
             for (int step = kKlShards; step > 0; step >>= 1)
                 if (k + step < nshard && s_pre[k + step] <= i) k += step;
-            q[t] = qin[(int64_t)k * qseg + (i - s_pre[k])];
-            live[t] = q[t].rows <= -3;
+            mq = qin[(int64_t)k * qseg + (i - s_pre[k])];
+        }
+        struct { int32_t gpos, coff; } q[S];
+        int64_t e[S];
+        int32_t n[S];
+        uint32_t rcode[S];
+        bool live[S], deep[S];
+        bool anydeep = false;
+#pragma unroll
+        for (int t = 0; t < S; t++) {
+            q[t].gpos = __builtin_amdgcn_readlane(mq.gpos, 16 * t);
+            q[t].coff = __builtin_amdgcn_readlane(mq.coff, 16 * t);
+            const int32_t rw = __builtin_amdgcn_readlane(mq.rows, 16 * t);
+            n[t] = 0;
+            e[t] = 0;
+            rcode[t] = 0;
+            live[t] = rw <= -3;
+            deep[t] = live[t] && -3 - rw > kKgpColCap;               // KL's coverage: the column may not fit in LDS
+            anydeep |= deep[t];
         }
 #pragma unroll
-        for (int t = 0; t < kKgSites; t++)
+        for (int t = 0; t < S; t++)
             if (live[t]) {
                 e[t] = (int64_t)blkA[q[t].gpos >> kRgBlockShift] & ~(int64_t)63;
                 rcode[t] = ref[q[t].gpos];
             }
         // chunk steps: every live site reads its next 64 entries' headers, then the covering ones' units (loading the
-        // next chunk's headers while this chunk's units are in flight measured no change, DESIGN.md 3 KG)
+        // next chunk's headers while this chunk's units are in flight measured no change, DESIGN.md 3 KGP)
         for (;;) {
             bool any = false;
 #pragma unroll
-            for (int t = 0; t < kKgSites; t++) any |= live[t];
+            for (int t = 0; t < S; t++) any |= live[t];
             if (!any) break;
-            int2 h[kKgSites];
-            int64_t gb[kKgSites];
+            int2 h[S];
+            int64_t gb[S];
 #pragma unroll
-            for (int t = 0; t < kKgSites; t++) {
+            for (int t = 0; t < S; t++) {
                 const bool l = live[t] && e[t] < n_entries;
                 h[t] = l ? rh[e[t] + lane] : make_int2(0x7FFFFFFF, 0);
                 gb[t] = l ? grp[e[t] >> 6].base : 0;
             }
-            uint64_t u[kKgSites];
-            int32_t o[kKgSites];
+            uint64_t u[S];
+            int32_t o[S];
 #pragma unroll
-            for (int t = 0; t < kKgSites; t++) {
+            for (int t = 0; t < S; t++) {
                 const int32_t p = q[t].gpos, gf = h[t].x, gl = h[t].y & 0x7FFFFFFF;
                 const bool covers = live[t] && gf <= p && p <= gl;
                 o[t] = covers ? p - gf : -1;
                 u[t] = covers ? units[gb[t] + (int64_t)(o[t] >> 3) * 64 + lane] : 0ull;
             }
 #pragma unroll
-            for (int t = 0; t < kKgSites; t++) {
+            for (int t = 0; t < S; t++) {
                 if (!live[t]) continue;
                 const int32_t p = q[t].gpos;
                 const uint32_t code = o[t] >= 0 ? (((uint32_t)(u[t] >> (8 * (o[t] & 7))) & 0xFFu) ^ rcode[t]) : 0u;
+                const uint32_t neg = (uint32_t)h[t].y >> 31;
                 const unsigned long long m = __ballot(code != 0);
                 if (code) {
-                    const int rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                    cols[((int64_t)q[t].coff << 2) + n[t] + rk] = (uint16_t)(code | (((uint32_t)h[t].y >> 31) << 8));
+                    const int at = n[t] + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                    if (deep[t]) cols[((int64_t)q[t].coff << 2) + at] = (uint16_t)(code | neg << 8);   // (KG's format)
+                    else if (at < kKgpColCap) s_col[wv][t][at] = (uint16_t)kgp_entry(code, neg, gp.max_q);
+                    if (code & 0x80u) atomicAdd(&s_tal[wv][t][((code >> 5) & 3u) + 4u * neg], 1);
                 }
                 n[t] += (int32_t)__popcll(m);
                 e[t] += 64;
-                if (__ballot(h[t].x > p) || e[t] >= n_entries) {   // entries are sorted by gfirst: none later covers p
+                if (__ballot(h[t].x > p) || e[t] >= n_entries) {        // sorted by gfirst: none later covers p
                     live[t] = false;
-                    q[t].rows = n[t];
+                    if (!deep[t] && lane < 3 && n[t] + lane < ((n[t] + 3) & ~3) && n[t] + lane < kKgpColCap)
+                        s_col[wv][t][n[t] + lane] = (uint16_t)kKgpPad;
                 }
             }
         }
+        // the columns are written: the deep ones in cols, read back below by other lanes of this wave
+        if (anydeep) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        }
+        wave_lds_sync();
+        int32_t maxrows = 0;
 #pragma unroll
-        for (int t = 0; t < kKgSites; t++)
-            if (lane == t && i0 + t < total) qout[i0 + t] = q[t];
+        for (int t = 0; t < S; t++) maxrows = n[t] > maxrows ? n[t] : maxrows;
+        if (maxrows == 0) continue;                                     // nothing to call (VariantDiscoverySNVQAlgorithm.java:101-103)
+#pragma unroll
+        for (int t = 0; t < S; t++) s_n[wv][t] = n[t];
+        wave_lds_sync();
+        const int32_t rows = s_n[wv][g];                                // = CountsHelper's total: every entry is a nonzero code
+        const bool mydeep = mq.rows <= -3 && -3 - mq.rows > kKgpColCap;
+        const uint16_t* const gcol = cols + ((int64_t)mq.coff << 2);
+        // the sum of lane j over its site's column in rank order, a window of kKgpColCap entries at a time.  A call
+        // that adds to no sum adds the tables' +0.0 here: the sums start at +0.0 and no sum of theirs is -0.0, so the
+        // bits are those of skipping it.
+        double L = 0;
+        const char* const tb = reinterpret_cast<const char*>(s_t);
+        for (int32_t base = 0; base < maxrows; base += kKgpColCap) {
+            if (anydeep) {
+                if (base > 0) wave_lds_sync();                           // the previous window is read
+                if (mydeep) {                                           // 8 entries per lane, within the reserved space
+                    const int32_t at = base + 8 * j;
+                    uint2 lo = make_uint2(0, 0), hi = make_uint2(0, 0);
+                    if (at < rows) lo = *reinterpret_cast<const uint2*>(gcol + at);
+                    if (at + 4 < rows) hi = *reinterpret_cast<const uint2*>(gcol + at + 4);
+                    const uint32_t w[4] = {lo.x, lo.y, hi.x, hi.y};
+                    uint32_t o[4];
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const uint32_t e0 = w[k] & 0xFFFFu, e1 = w[k] >> 16;
+                        const uint32_t c0 = at + 2 * k < rows ? kgp_entry(e0 & 0xFFu, (e0 >> 8) & 1u, gp.max_q) : kKgpPad;
+                        const uint32_t c1 = at + 2 * k + 1 < rows ? kgp_entry(e1 & 0xFFu, (e1 >> 8) & 1u, gp.max_q) : kKgpPad;
+                        o[k] = c0 | c1 << 16;
+                    }
+                    *reinterpret_cast<uint4*>(mycol + 8 * j) = make_uint4(o[0], o[1], o[2], o[3]);
+                }
+                wave_lds_sync();
+            }
+            const int32_t lim = rows - base;
+            const int32_t wn = maxrows - base < kKgpColCap ? maxrows - base : kKgpColCap;
+            for (int32_t r = 0; r < wn; r += 4) {
+                if (r >= lim) continue;                                 // past the lane's site's column
+                const uint2 d = *reinterpret_cast<const uint2*>(mycol + r);
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const uint32_t w = k < 2 ? d.x : d.y;
+                    const uint32_t a8 = __builtin_amdgcn_ubfe(w, 9 + 16 * (k & 1), 5);            // 8 x allele
+                    const uint32_t q8 = ((k & 1) ? w >> 16 : w) & 0x1F8u;                         // 8 x capped quality
+                    L += *reinterpret_cast<const double*>(tb + ((__builtin_amdgcn_ubfe(lut, a8, 8) << 3) + q8));
+                }
+            }
+        }
+        // posterior: lane k of the site owns event k (getPosteriorProbabilities, CountsHelper.java:410-443: row i holds
+        // (i,i) then (i,j) for j != i ascending; L is symmetric, so (j,i) has (i,j)'s exponent and its pow's bits)
+        const uint32_t rc = (uint32_t)mq.rc;
+        const bool callable = (rc & 0x80u) != 0;
+        const bool call = rows > 0 && callable && !ABLATE(gp.ablate, 8);
+        if (!__ballot(call)) continue;
+        Lw[slot] = L;
+        wave_lds_sync();
+        const double ev = gL[(int)((0x8639852765143210ull >> (4 * j)) & 15ull)] +
+                          ((j & 3) == 0 ? gp.log_prior_homo : gp.log_prior_hetero);
+        // calculatePosteriorProbabilities (:472-495): logMax is the first event, then replaced while positive or
+        // smaller than the next.  With no positive event (log-probabilities) that is the maximum, taken across the
+        // group's lanes; otherwise every lane walks the group's events in Java's order
+        double logMax;
+        if (!__ballot(ev > 0)) {
+            logMax = fmax(ev, dpp_f64<0x140>(ev));                       // row_mirror: lane 15 - j
+            logMax = fmax(logMax, dpp_f64<0x141>(logMax));               // row_half_mirror: lane 7 - j of the half
+            logMax = fmax(logMax, dpp_f64<0xB1>(logMax));                // quad_perm 1,0,3,2
+            logMax = fmax(logMax, dpp_f64<0x4E>(logMax));                // quad_perm 2,3,0,1
+        } else {
+            evw[slot] = ev;
+            wave_lds_sync();
+            logMax = 1;
+            for (int k = 0; k < 16; k++) {
+                const double x = ge[k];
+                if (logMax > 0 || logMax < x) logMax = x;
+            }
+            wave_lds_sync();
+        }
+        // events more than 20 below the maximum are 0 (and add +0.0 to the normaliser, which is at least +0.0: the bits
+        // of skipping them); every lane sums the group's 16 in Java's order
+        const double x = ev - logMax;
+        const bool on = !(x < -20);
+        const double pk = on ? kgp_pow10(x) : 0.0;
+        evw[slot] = pk;
+        wave_lds_sync();
+        double totalProb = 0;
+#pragma unroll
+        for (int k = 0; k < 16; k++) totalProb += ge[k];
+        wave_lds_sync();
+        evw[slot] = on ? pk / totalProb : 0.0;
+        wave_lds_sync();
+        // post(i, j) is event 4i + (j < i ? j + 1 : j) for j != i, 4i for j == i
+        auto post = [&](int i, int k) -> double { return ge[i == k ? 4 * i : 4 * i + (k < i ? k + 1 : k)]; };
+        // getIndexesMaxGenotype (VariantDiscoverySNVQAlgorithm.java:223-243), default index = reference
+        const int refIdx = (int)((rc >> 5) & 3u);
+        int I = refIdx, J = refIdx;
+        const double refProb = post(refIdx, refIdx);
+        double probMax = refProb;
+#pragma unroll
+        for (int pi = 0; pi < 4; pi++)
+#pragma unroll
+            for (int pj = pi; pj < 4; pj++) {
+                double gpr = ge[pi == pj ? 4 * pi : 4 * pi + pj];          // (pi, pj), pj > pi
+                if (pi != pj) gpr += ge[4 * pj + pi + 1];                  // (pj, pi), pi < pj
+                if (gpr > probMax + 0.01) { probMax = gpr; I = pi; J = pj; }
+            }
+        int8_t genotype = -1, alt = -1, third = -1, nal = 0;
+        // GQ in the group's even lanes, QUAL in its odd ones: one pass of phred for both (lane 0 writes the record)
+        const int ph = kgp_phred((j & 1) ? refProb : 1 - probMax);
+        const int16_t gq = (int16_t)ph, qual = (int16_t)__builtin_amdgcn_update_dpp(ph, ph, 0xB1, 0xF, 0xF, false);
+        bool keep = false;
+        if (I != J && I != refIdx && J != refIdx) {               // triallelic (:128-177)
+            if (post(I, I) > post(J, J) + 0.01) { alt = (int8_t)I; third = (int8_t)J; }
+            else { alt = (int8_t)J; third = (int8_t)I; }
+            nal = 3; genotype = 3; keep = true;
+        } else if (I != J) {
+            alt = (int8_t)(refIdx != I ? I : J); nal = 2; genotype = 1; keep = true;
+        } else if (refIdx != I) {
+            alt = (int8_t)I; nal = 2; genotype = 2; keep = true;
+        }                                                         // else hom-ref: dropped (SingleSampleVariantPileupListener.java:223)
+        if (keep && gp.min_quality > gq) keep = false;
+        // the record goes to its position bucket (KO orders each bucket): the group's first lane lays the 64-B SiteRec
+        // out in LDS (the site's column is read) and takes the slot, the 16 lanes store a dword each
+        uint32_t* const st = reinterpret_cast<uint32_t*>(mycol);
+        if (j == 0) {
+            const int32_t gpos = mq.gpos;
+            const int32_t bk = gpos >> shift;
+            const int32_t k = call && keep ? atomicAdd(&bcount[bk], 1) : bcap;
+            int64_t at = -1;                                            // no record, or the bucket overflowed: the host grows the buckets and reruns
+            if (k < bcap) {
+                at = (int64_t)bk * bcap + k;
+                // ngsep_site_out's header dwords (put_site): seq, gpos, ref|n_alleles|alt|third, genotype|strand_bias|gq,
+                // qual|is_call|pool, dp, counts[4], strand_counts[4][2]
+                const uint32_t h2 = (uint32_t)(uint8_t)"ACGT"[refIdx] | (uint32_t)(uint8_t)nal << 8 | (uint32_t)(uint8_t)alt << 16 |
+                                    (uint32_t)(uint8_t)third << 24;
+                const uint32_t h3 = (uint32_t)(uint8_t)genotype | 0xFF00u | (uint32_t)(uint16_t)gq << 16;
+                const uint32_t h4 = (uint32_t)(uint16_t)qual | 1u << 16;
+                const int32_t* const tal = s_tal[wv][g];
+                int2 c[4];                                              // counts[a], countsStrand[a][0]
+#pragma unroll
+                for (int a = 0; a < 4; a++) c[a] = make_int2(tal[a] + tal[4 + a], tal[4 + a]);
+                uint32_t big = 0;
+#pragma unroll
+                for (int a = 0; a < 4; a++) big |= (uint32_t)c[a].x | (uint32_t)c[a].y | (uint32_t)(c[a].x - c[a].y);
+                // whole records (multi-allelic, full_records, counts past 65535) go to ext, the SiteRec pointing there
+                const bool whole = gp.full_records != 0 || nal != 2 || big > 0xFFFFu;
+                st[0] = 0xFFFFFFFFu;
+                st[1] = (uint32_t)gpos;
+                st[2] = h2;
+                st[3] = h3;
+                st[4] = h4 | (whole ? (uint32_t)kRecExt << 16 : 0u);
+                st[5] = (uint32_t)rows;
+                st[6] = ((uint32_t)c[0].x & 0xFFFFu) | (uint32_t)c[1].x << 16;
+                st[7] = ((uint32_t)c[2].x & 0xFFFFu) | (uint32_t)c[3].x << 16;
+                if (whole) {
+                    const unsigned long long e = atomicAdd(ext_n, 1ull);
+                    if ((int64_t)e < ext_cap) {
+                        uint32_t* o = reinterpret_cast<uint32_t*>(ext + e);
+                        o[0] = 0xFFFFFFFFu; o[1] = (uint32_t)gpos; o[2] = h2; o[3] = h3; o[4] = h4; o[5] = (uint32_t)rows;
+#pragma unroll
+                        for (int a = 0; a < 4; a++) {
+                            o[6 + a] = (uint32_t)c[a].x;
+                            o[10 + 2 * a] = (uint32_t)c[a].y;
+                            o[11 + 2 * a] = (uint32_t)(c[a].x - c[a].y);
+                        }
+                        for (int t = 0; t < 10; t++) {
+                            const uint2 bits = __builtin_bit_cast(uint2, gL[t]);
+                            o[18 + 2 * t] = bits.x;
+                            o[19 + 2 * t] = bits.y;
+                        }
+                    }
+                    st[8] = st[9] = 0;
+                    st[10] = (uint32_t)e;
+                    st[11] = (uint32_t)(e >> 32);
+                    st[12] = st[13] = st[14] = st[15] = 0;
+                } else {
+                    auto tri = [](int i, int k2) {
+                        const int a = i < k2 ? i : k2, b = i < k2 ? k2 : i;
+                        return (a == 0 ? 0 : a == 1 ? 4 : a == 2 ? 7 : 9) + (b - a);
+                    };
+                    st[8] = ((uint32_t)tal[4 + refIdx] & 0xFFFFu) | (uint32_t)tal[refIdx] << 16;
+                    st[9] = ((uint32_t)tal[4 + alt] & 0xFFFFu) | (uint32_t)tal[alt] << 16;
+                    double* const sd = reinterpret_cast<double*>(st + 10);
+                    sd[0] = gL[tri(refIdx, refIdx)];
+                    sd[1] = gL[tri(refIdx, alt)];
+                    sd[2] = gL[tri(alt, alt)];
+                }
+            }
+            *reinterpret_cast<int64_t*>(st + 16) = at;
+        }
+        wave_lds_sync();
+        {
+            const int64_t at = *reinterpret_cast<const int64_t*>(st + 16);
+            if (at >= 0) reinterpret_cast<uint32_t*>(brec + at)[j] = st[j];
+        }
     }
 }
 
@@ -3924,43 +4218,46 @@ static int enqueue_run(Device* d, RunSlot& sl, const Staged& s, const LikTables&
         sl.scan_timed = k0 != nullptr;
         kg_sites = s.g_len;
     }
-    {
-        // KG: the queued sites' columns, one wave per site (grid-stride past the estimate)
-        const int64_t nblk = std::max<int64_t>(d->n_cu, std::min<int64_t>((kg_sites + 3) / 4, (int64_t)d->n_cu * 32));
-        static const int kg_env = diag_env("NGSEP_KG_SITES") ? std::atoi(diag_env("NGSEP_KG_SITES")) : 4;   // tuning
-        const int kgs = kg_env == 8 ? 8 : kg_env == 2 ? 2 : 4;
-        if (kl_run)
-            hipLaunchKernelGGL(kgs == 8 ? k_gather_kl<8> : kgs == 2 ? k_gather_kl<2> : k_gather_kl<4>,
-                               dim3((unsigned)std::max<int64_t>(d->n_cu, std::min<int64_t>((kg_sites + 4 * kgs - 1) / (4 * kgs), (int64_t)d->n_cu * 32))),
-                               dim3(256), 0, sl.stream, (const SiteQ*)sl.d_hard, (const unsigned long long*)(ctr + kCtrShard0), kCtrShardStride,
-                               kKlShards, sl.cap_hard / kKlShards, sl.d_hard2, (const int2*)d->d_rh, (const RGroup*)d->d_grp,
-                               (const uint64_t*)d->d_units, (const int32_t*)d->d_blkA, (const uint8_t*)d->d_ref, d->n_entries, sl.d_cols, ctr);
-        else
-        hipLaunchKernelGGL(k_gather_cols, dim3((unsigned)nblk), dim3(256), 0, sl.stream, (const SiteQ*)sl.d_hard,
-                           (const unsigned long long*)(kl_run ? ctr + kCtrShard0 : ctr + 2), kl_run ? kCtrShardStride : 1,
-                           kl_run ? kKlShards : 1, kl_run ? sl.cap_hard / kKlShards : sl.cap_hard, sl.d_hard2,
-                           (const int2*)d->d_rh, (const RGroup*)d->d_grp,
-                           (const uint64_t*)d->d_units, (const int32_t*)d->d_blkA, (const uint8_t*)d->d_ref, d->n_entries, sl.d_cols,
-                           sl.cap_cols, ctr);
+    if (kl_run && g.ploidy < 3 && !g.dump_all) {
+        // KGP: KL's survivors gathered and called by one kernel, four sites per wave (grid-stride past the estimate)
+        const int64_t nblk = std::max<int64_t>(d->n_cu, std::min<int64_t>((kg_sites + 4 * kKgpSites - 1) / (4 * kKgpSites), (int64_t)d->n_cu * 32));
+        hipExtLaunchKernelGGL(k_gather_call, dim3((unsigned)nblk), dim3(256), 0, sl.stream,
+                              d->time_posterior ? sl.ev[5] : nullptr, d->time_posterior ? sl.ev[2] : nullptr, 0,
+                              (const SiteQ*)sl.d_hard, (const unsigned long long*)(ctr + kCtrShard0), kCtrShardStride, kKlShards,
+                              sl.cap_hard / kKlShards, (const int2*)d->d_rh, (const RGroup*)d->d_grp, (const uint64_t*)d->d_units,
+                              (const int32_t*)d->d_blkA, (const uint8_t*)d->d_ref, d->n_entries, sl.d_cols, ctr,
+                              (const LikTables*)sl.d_tables, g, sl.d_brec, sl.d_bcount, shift, bcap, sl.d_ext, ctr + 4, sl.cap_ext);
+        HIP_TRY(launch_check());
+    } else {
+        {
+            // KG: the queued sites' columns, one wave per site (grid-stride past the estimate)
+            const int64_t nblk = std::max<int64_t>(d->n_cu, std::min<int64_t>((kg_sites + 3) / 4, (int64_t)d->n_cu * 32));
+            hipLaunchKernelGGL(k_gather_cols, dim3((unsigned)nblk), dim3(256), 0, sl.stream, (const SiteQ*)sl.d_hard,
+                               (const unsigned long long*)(kl_run ? ctr + kCtrShard0 : ctr + 2), kl_run ? kCtrShardStride : 1,
+                               kl_run ? kKlShards : 1, kl_run ? sl.cap_hard / kKlShards : sl.cap_hard, sl.d_hard2,
+                               (const int2*)d->d_rh, (const RGroup*)d->d_grp,
+                               (const uint64_t*)d->d_units, (const int32_t*)d->d_blkA, (const uint8_t*)d->d_ref, d->n_entries, sl.d_cols,
+                               sl.cap_cols, ctr);
+            HIP_TRY(launch_check());
+        }
+        // one lane per queued site: enough workgroups for the queue (the count is on the device; sized from the
+        // previous run's survivors, grid-stride beyond)
+        static const int kp_env = diag_env("NGSEP_KP_GRID") ? std::max(1, std::atoi(diag_env("NGSEP_KP_GRID"))) : 0;   // tuning
+        const int kp_grid = kp_env ? kp_env : (int)std::max<int64_t>(d->n_cu, std::min<int64_t>((d->last_hard + kPostThreads - 1) / kPostThreads, 8 * (int64_t)d->n_cu));
+        if (g.ploidy >= 3 && !g.dump_all) {
+            if (!d->pool_valid) { err = "ploidy >= 3 without pool tables (device_set_pool)"; return -1; }
+            hipExtLaunchKernelGGL(k_posterior_pool, dim3(kp_grid), dim3(kPostThreads), 0, sl.stream,
+                                  d->time_posterior ? sl.ev[5] : nullptr, d->time_posterior ? sl.ev[2] : nullptr, 0,
+                                  (const SiteQ*)sl.d_hard2, (const unsigned long long*)(ctr + 2), sl.cap_hard, (const uint16_t*)sl.d_cols,
+                                  (const PoolTables*)d->d_pool, g, sl.d_brec, sl.d_bcount, shift, bcap, sl.d_ext, ctr + 4, sl.cap_ext);
+        } else {
+            hipExtLaunchKernelGGL(k_posterior, dim3(kp_grid), dim3(kPostThreads), 0, sl.stream,
+                                  d->time_posterior ? sl.ev[5] : nullptr, d->time_posterior ? sl.ev[2] : nullptr, 0,
+                                  (const SiteQ*)sl.d_hard2, (const unsigned long long*)(ctr + 2), sl.cap_hard, (const uint16_t*)sl.d_cols,
+                                  (const LikTables*)sl.d_tables, g, sl.d_brec, sl.d_bcount, shift, bcap, sl.d_ext, ctr + 4, sl.cap_ext);
+        }
         HIP_TRY(launch_check());
     }
-    // one lane per queued site: enough workgroups for the queue (the count is on the device; sized from the
-    // previous run's survivors, grid-stride beyond)
-    static const int kp_env = diag_env("NGSEP_KP_GRID") ? std::max(1, std::atoi(diag_env("NGSEP_KP_GRID"))) : 0;   // tuning
-    const int kp_grid = kp_env ? kp_env : (int)std::max<int64_t>(d->n_cu, std::min<int64_t>((d->last_hard + kPostThreads - 1) / kPostThreads, 8 * (int64_t)d->n_cu));
-    if (g.ploidy >= 3 && !g.dump_all) {
-        if (!d->pool_valid) { err = "ploidy >= 3 without pool tables (device_set_pool)"; return -1; }
-        hipExtLaunchKernelGGL(k_posterior_pool, dim3(kp_grid), dim3(kPostThreads), 0, sl.stream,
-                              d->time_posterior ? sl.ev[5] : nullptr, d->time_posterior ? sl.ev[2] : nullptr, 0,
-                              (const SiteQ*)sl.d_hard2, (const unsigned long long*)(ctr + 2), sl.cap_hard, (const uint16_t*)sl.d_cols,
-                              (const PoolTables*)d->d_pool, g, sl.d_brec, sl.d_bcount, shift, bcap, sl.d_ext, ctr + 4, sl.cap_ext);
-    } else {
-        hipExtLaunchKernelGGL(k_posterior, dim3(kp_grid), dim3(kPostThreads), 0, sl.stream,
-                              d->time_posterior ? sl.ev[5] : nullptr, d->time_posterior ? sl.ev[2] : nullptr, 0,
-                              (const SiteQ*)sl.d_hard2, (const unsigned long long*)(ctr + 2), sl.cap_hard, (const uint16_t*)sl.d_cols,
-                              (const LikTables*)sl.d_tables, g, sl.d_brec, sl.d_bcount, shift, bcap, sl.d_ext, ctr + 4, sl.cap_ext);
-    }
-    HIP_TRY(launch_check());
     // order the records by position on the device (one kernel; counters[0] = records | max bucket << 40)
     hipLaunchKernelGGL(ko_fused, dim3((unsigned)((nb + kKofBuckets - 1) / kKofBuckets)), dim3(64 * kKofBuckets), 0, sl.stream, sl.d_brec,
                        (const int32_t*)sl.d_bcount, nb, bcap, ctr, sl.d_sorted, sl.cap, d->d_wins, d->n_wins, 1 << shift);
